@@ -10,11 +10,17 @@ chip idle.  With N > 1 ranks every step is a tree of N * 2^16 leaves: each rank 
 2^16-leaf subtree (no data-path collective), the N sub-roots are exchanged with one RCCL all_gather
 (N x 32 bytes per tree) and the log2(N) top levels are hashed on every rank - weak scaling.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line of at most 8 KB on stdout (benchlib/line.py holds it to that: round 5's
+A plain run (no --full) does what the headline needs and nothing else: set-up, the --warmup steps, --preheat-s of the
+timed call (untimed), ONE region of exactly --steps steps between fences, the outputs of its last step if
+--dump-outputs is given, and the line with `value` (hashes/s over that region) and `ms_per_step`.  Everything below -
+the sustained window, telemetry, roofline, airfri, the CPU baselines, extras, the process-group report and the
+detail file - runs with --full.
+
+With --full, rank 0 prints ONE JSON line of at most 8 KB on stdout (benchlib/line.py holds it to that: round 5's
 20 KB line could not be parsed by the driver) and writes everything else it measured - telemetry
 windows, burst, region percentiles, per-phase tables, configs[2] timings, provenance - to
 bench_detail.json beside this script and to stderr.  `value` = Pedersen hashes/s over the whole job.
@@ -49,9 +55,10 @@ sys.path.insert(0, ROOT)
 
 from benchlib import telemetry as _telemetry  # noqa: E402  (no torch import, no GPU touched at import time)
 from benchlib.common import HEIGHT, median, seeded_felts  # noqa: E402
+from benchlib.dump import merkle_outputs, write_outputs  # noqa: E402
 from benchlib.launch import dist_report, init_library_one_plan, open_process_group, reduce_scalar, self_spawn  # noqa: E402
 from benchlib.line import emit, main_line  # noqa: E402
-from benchlib.merkle import combine_check, merkle_detail, plan  # noqa: E402
+from benchlib.merkle import combine_check, merkle_detail, merkle_plain, plan  # noqa: E402
 from benchlib.provenance import build_provenance  # noqa: E402
 from benchlib.telemetry import Telemetry  # noqa: E402,F401  (re-exported: tests and tools read bench.Telemetry)
 
@@ -254,20 +261,28 @@ def parse_args():
     ap.add_argument("--log-rows", type=int, default=20, help="airfri workload: log2 of the trace rows per GPU")
     ap.add_argument("--with-witness", action="store_true",
                     help="airfri workload: generate the trace (witness) inside every job instead of as input preparation")
+    ap.add_argument("--full", action="store_true",
+                    help="merkle workload: everything beyond the headline - burst and sustained windows (value = median "
+                         "region), telemetry, roofline, CPU baselines, airfri, extras, the process-group report - and "
+                         "the detail file.  Without it: warm-up, pre-heat, ONE region of exactly --steps steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="merkle workload: after the timed steps, write what the last step computed (its tree's inner "
+                         "nodes and the job root, felts as eight 32-bit words in float64) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--force-dist", action="store_true", default=os.environ.get("STARKPERP_BENCH_FORCE_DIST") == "1",
                     help="--gpus 1 only: create a world-size-1 RCCL process group anyway and take every branch the N > 1 "
                          "runs take - the one-GPU rehearsal of the multi-GPU launch")
     ap.add_argument("--min-timed-s", type=float, default=float(os.environ.get("STARKPERP_BENCH_MIN_TIMED_S", "3.0")),
-                    help="the timed regions (each EXACTLY --steps steps between fences) are repeated until this many "
-                         "seconds have been timed; value = the median region of that sustained window")
+                    help="--full: the timed regions (each EXACTLY --steps steps between fences) are repeated until this "
+                         "many seconds have been timed; value = the median region of that sustained window")
     ap.add_argument("--preheat-s", type=float, default=float(os.environ.get("STARKPERP_BENCH_PREHEAT_S", "1.0")),
-                    help="seconds of the timed call itself issued (untimed) in front of the sustained window, so that "
-                         "the power controller has settled (profiles/r03_power_clock_bulk.txt: ~0.7 s)")
+                    help="seconds of the timed call itself issued (untimed) after the warm-up steps, in front of the timed "
+                         "region (--full: the sustained window), so that the power controller has settled "
+                         "(profiles/r03_power_clock_bulk.txt: ~0.7 s)")
     ap.add_argument("--burst-s", type=float, default=0.05,
-                    help="the 50 ms window of rounds 1 - 4, taken first, straight out of idle: reported as `burst`")
-    ap.add_argument("--no-airfri", action="store_true", help="merkle workload: skip the `airfri` object")
+                    help="--full: the 50 ms window of rounds 1 - 4, taken first, straight out of idle: reported as `burst`")
+    ap.add_argument("--no-airfri", action="store_true", help="merkle workload with --full: skip the `airfri` object")
     return ap.parse_args()
 
 
@@ -284,6 +299,13 @@ def main():
             # would, and hand their single JSON line through
             return self_spawn(args.gpus)
         raise SystemExit("WORLD_SIZE=%d does not match --gpus %d" % (world, args.gpus))
+    # stdout carries the JSON line and nothing else: the line keeps its own handle on it, and fd 1 goes to stderr for
+    # the rest of the run, so that what native libraries print there (RCCL's version banner, whenever a communicator
+    # comes up or goes down) cannot land beside the line.
+    sys.stdout.flush()
+    line_out = os.fdopen(os.dup(1), "w")
+    os.dup2(2, 1)
+    sys.stdout = line_out
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (no CPU fallback)")
     # Test hook for boxes with ONE GPU (tests/test_gpu_bench_ranks.py): every rank on device 0 and the
@@ -298,7 +320,8 @@ def main():
     from starkperp import _lib
     from starkperp.distributed import combine_forest_dev
     lib, wide_error = init_library_one_plan(torch, dist, dev, dev_index, args.window_bits)
-    tel = _telemetry.ACTIVE = Telemetry(dev_index).start() if rank == 0 else None
+    with_tel = rank == 0 and (args.full or args.workload == "airfri")
+    tel = _telemetry.ACTIVE = Telemetry(dev_index).start() if with_tel else None
     if args.workload == "airfri":
         from benchlib.airfri import run_airfri
         return run_airfri(args, torch, dist, lib, _lib, dev, rank, world, cpu_leg=cpu_airfri_baseline)
@@ -349,28 +372,6 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    for _ in slots:  # size every stream's scratch before the timed region
-        issue(max_b)
-    for nb in plan(args.warmup, B):
-        issue(nb)
-    fence()
-    # The inner nodes of the buffers the TIMED calls write are zeroed first, so that the parity legs below
-    # (cpu_baseline*, matches_gpu / root_matches_gpu) check what the timed region itself computed.
-    first_timed = call_counter[0]
-    timed_targets = []
-    for i, nb in enumerate(timed_plan):
-        sl = slots[(first_timed + i) % n_streams]
-        if (id(sl), nb) not in [(id(a), b) for a, b in timed_targets]:
-            timed_targets.append((sl, nb))
-            sl["levels"][nb][n_leaves * nb:] = 0
-    fence()
-    # One region = EXACTLY --steps steps between two fences (barrier + synchronize on both sides); a region of 20
-    # lockstep trees lasts ~1.7 ms.  Three windows of such regions, one after the other:
-    #   burst      --burst-s (50 ms) straight after the CPU-only set-up: what rounds 1 - 4 reported;
-    #   pre-heat   --preheat-s (1 s) of the same call, untimed: the power controller settles;
-    #   sustained  regions repeated until --min-timed-s (3 s) have been timed: `value` = the MEDIAN region of this
-    #              window, with the shader clock and package power sampled beside it (Telemetry).
-    # Every rank takes the same decisions: a region's time is MAX-reduced over the ranks before it is used.
     MAX_REGIONS = 1 << 15
     local_regions = []  # this rank's own clock for every region (the MAX over ranks is what `value` uses)
 
@@ -399,6 +400,45 @@ def main():
                    "profile_end")
         return regs, window, (k_ms.value, int(k_launches.value), int(k_units.value))
 
+    for _ in slots:  # size every stream's scratch before the timed region
+        issue(max_b)
+    for nb in plan(args.warmup, B):
+        issue(nb)
+    fence()
+    preheat_regions = run_regions(args.preheat_s, MAX_REGIONS)[0] if args.preheat_s > 0 and not args.full else []
+    # The inner nodes of the buffers the TIMED calls write are zeroed first, so that the parity legs below
+    # (cpu_baseline*, matches_gpu / root_matches_gpu) and --dump-outputs see what the timed region itself computed.
+    first_timed = call_counter[0]
+    timed_targets = []
+    for i, nb in enumerate(timed_plan):
+        sl = slots[(first_timed + i) % n_streams]
+        if (id(sl), nb) not in [(id(a), b) for a, b in timed_targets]:
+            timed_targets.append((sl, nb))
+            sl["levels"][nb][n_leaves * nb:] = 0
+    fence()
+    if not args.full:
+        # A plain run: the warm-up steps and the pre-heat above, then ONE region of exactly --steps steps between two
+        # fences (MAX-reduced over the ranks), the outputs if asked for, the line.
+        t0 = time.perf_counter()
+        for nb in timed_plan:
+            issue(nb)
+        fence()
+        region = reduce_scalar(torch, dist, dev, time.perf_counter() - t0, "MAX")
+        if rank == 0:
+            if args.dump_outputs:
+                write_outputs(args.dump_outputs, merkle_outputs(slots[(call_counter[0] - 1) % n_streams], world))
+            emit(merkle_plain(args, world, lib, region, sum(preheat_regions), timed_plan, n_streams, wide_error))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    # --full.  One region = EXACTLY --steps steps between two fences (barrier + synchronize on both sides); a region of
+    # 20 lockstep trees lasts ~1.7 ms.  Three windows of such regions, one after the other:
+    #   burst      --burst-s (50 ms) straight after the CPU-only set-up: what rounds 1 - 4 reported;
+    #   pre-heat   --preheat-s (1 s) of the same call, untimed: the power controller settles;
+    #   sustained  regions repeated until --min-timed-s (3 s) have been timed: `value` = the MEDIAN region of this
+    #              window, with the shader clock and package power sampled beside it (Telemetry).
+    # Every rank takes the same decisions: a region's time is MAX-reduced over the ranks before it is used.
     m = {"timed_plan": timed_plan, "n_streams": n_streams, "trees_per_call_cap": B,
          "idle_tel": tel.window(time.perf_counter() - 0.5, time.perf_counter()) if tel else None}
     m["burst_regions"], m["burst_window"], m["burst_prof"] = profiled(args.burst_s, 64, 64)
@@ -406,6 +446,8 @@ def main():
     est = args.min_timed_s / max(median(m["burst_regions"]), 1e-5) * 1.25 + 16
     del local_regions[:]
     m["regions"], m["sustained_window"], m["prof"] = profiled(args.min_timed_s, MAX_REGIONS, est)
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, merkle_outputs(slots[(call_counter[0] - 1) % n_streams], world))
     local_value = (n_leaves - 1) * args.steps / median(local_regions)  # this rank's own subtrees over its own clock
 
     # The AIR + FRI half of the metric at N > 1: independent 2^20-row jobs on every GPU (BASELINE north_star:

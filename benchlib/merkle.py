@@ -73,6 +73,47 @@ def kernel_roofline(prof, wbits, config_key, value_per_gpu, held_mhz, share_of_h
     return roof
 
 
+def merkle_plain(args, world, lib, region_s, preheat_s, timed_plan, n_streams, wide_error=None):
+    """The line of a plain run (no --full): ONE region of exactly --steps steps between fences, after the warm-up steps
+    and the pre-heat; nothing else is measured."""
+    hashes_per_step = world * ((1 << HEIGHT) - 1) + (world - 1)
+    config = {
+        "workload": "2^16-leaf Pedersen Merkle rebuild per GPU (BASELINE.json configs[1]), %d rebuilds in lockstep"
+                    % max(timed_plan),
+        "tree_height": HEIGHT,
+        "leaves_per_gpu": 1 << HEIGHT,
+        "hashes_per_step": hashes_per_step,
+        "trees_in_timed_call": timed_plan[0] if len(set(timed_plan)) == 1 else max(timed_plan),
+        "calls_per_region": len(timed_plan),
+        "streams": n_streams,
+        "window_bits": int(lib.sp_window_bits()),
+        "table_gib": lib.sp_table_bytes() / 2**30,
+        "combine": "none" if world == 1 else "all_gather of %d sub-roots (RCCL) + %d top hashes" % (world, world - 1),
+    }
+    if wide_error:
+        config["window_plan_fallback"] = wide_error
+    return {
+        "metric": "pedersen_hashes_per_sec",
+        "value": hashes_per_step * args.steps / region_s,
+        "unit": "hashes/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": region_s / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": DTYPE,
+        "data": "synthetic",
+        "config": config,
+        "timed": {"regions": 1, "steps": args.steps, "total_s": region_s, "preheat_s": preheat_s,
+                  "value_is": "one region of exactly --steps steps between fences, after the warm-up steps and the "
+                              "pre-heat (--full: the median region of a sustained window, roofline, CPU legs, extras)"},
+        "roofline": None,
+        "cpu_baseline": None,
+    }
+
+
 def merkle_detail(args, world, lib, tel, m):
     """The full result of the headline workload.  `m`: what the timed region measured (see bench.py main):
     regions, preheat_regions, burst_regions, burst_prof, prof, windows (perf_counter pairs), timed_plan, n_streams,

@@ -281,3 +281,82 @@ def test_c3_roofline_uses_live_rates_where_given():
     for key in ("message_hash_chains", "tree_paths", "verify_keyed_4096"):
         assert c[key]["rate_is"].startswith("the counter pass") and 0 < c[key]["frac"] < 1
         assert 1.5 < c[key]["ns_per_dependent_instr"] < 6
+
+
+def test_full_and_dump_outputs_options(monkeypatch):
+    """A plain run is the default; --full opts into everything beyond the headline, --dump-outputs names a directory."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_plain_line_is_complete_and_counts_exactly_the_steps():
+    """The line of a plain run: the contract's keys, value and ms_per_step from ONE region of exactly --steps steps."""
+    from benchlib import merkle
+
+    class Lib:
+        def sp_window_bits(self):
+            return 26
+
+        def sp_table_bytes(self):
+            return 75 << 30
+
+    class Args:
+        steps, warmup = 40, 5
+    out = merkle.merkle_plain(Args, 1, Lib(), 0.004, 1.0, [20, 20], 2)
+    back = json.loads(line.check_line(line._clean(out), roofline_required=False))
+    for k in line.REQUIRED_KEYS:
+        assert k in back, k
+    assert back["metric"] == "pedersen_hashes_per_sec" and back["unit"] == "hashes/s" and back["dtype"] == common.DTYPE
+    assert back["higher_is_better"] is True and back["steps"] == 40 and back["warmup"] == 5
+    assert back["ms_per_step"] == pytest.approx(0.1) and back["value"] == pytest.approx(40 * 65535 / 0.004)
+    assert back["timed"]["regions"] == 1 and back["timed"]["steps"] == 40
+    assert back["config"]["calls_per_region"] == 2 and back["config"]["table_gib"] == 75.0
+    two = merkle.merkle_plain(Args, 2, Lib(), 0.004, 1.0, [20, 20], 2)
+    assert two["config"]["hashes_per_step"] == 2 * 65535 + 1 and two["value"] == pytest.approx(40 * 131071 / 0.004)
+
+
+def test_dump_outputs_take_the_last_tree_bit_exact(tmp_path):
+    """--dump-outputs: the last tree of a level-major forest buffer (sp_merkle_forest_dev's layout), every felt as eight
+    32-bit words held exactly in float64; with N > 1 ranks the root is the job root from the top forest."""
+    import numpy as np
+    import torch
+    from benchlib import dump
+
+    height, nb = 3, 3
+    rows = nb * (2 * (1 << height) - 1)
+    # felt = (level, tree, index) spread over all four limbs, top limb near 2^58 (felts are < 2^251)
+    ids = []
+    for k in range(height + 1):
+        for t in range(nb):
+            for i in range(1 << (height - k)):
+                ids.append((k, t, i))
+    assert len(ids) == rows
+
+    def felt(k, t, i):
+        return (((k << 50) | (t << 40) | (i << 30) | 0x155) << 192) | (0xDEADBEEF << 96) | (0xFFFFFFFF << 32) | (k + 7)
+    vals = [felt(*x) for x in ids]
+    limbs = [[(v >> (64 * j)) & ((1 << 64) - 1) for j in range(4)] for v in vals]
+    levels = torch.tensor([[l - (1 << 64) if l >= 1 << 63 else l for l in row] for row in limbs], dtype=torch.int64)
+
+    def back(a):
+        return [sum(int(w) << (32 * j) for j, w in enumerate(r)) for r in a]
+
+    f = dump.felts_f64(levels)
+    assert f.dtype == np.float64 and f.shape == (rows, 8) and back(f) == vals
+    nodes = dump.tree_inner_nodes(levels, nb, nb - 1, height)
+    want = [felt(k, nb - 1, i) for k in range(1, height + 1) for i in range(1 << (height - k))]
+    assert nodes.shape == ((1 << height) - 1, 8) and back(nodes) == want
+    one = dump.merkle_outputs({"last_nb": nb, "levels": {nb: levels}}, 1, height)
+    assert back(one["merkle_last_tree_root"]) == [felt(height, nb - 1, 0)]
+    world = 2  # top forest of nb trees of height 1: world * nb gathered sub-roots, then the nb job roots
+    top = torch.arange(4 * nb * (2 * world - 1), dtype=torch.int64).reshape(-1, 4)
+    two = dump.merkle_outputs({"last_nb": nb, "levels": {nb: levels}, "top": top}, world, height)
+    assert back(two["merkle_last_tree_root"]) == back(dump.felts_f64(top[nb * (2 * world - 1) - 1:]))
+    paths = dump.write_outputs(str(tmp_path / "out"), two)
+    assert sorted(os.path.basename(p) for p in paths) == ["merkle_last_tree_inner_nodes.npy", "merkle_last_tree_root.npy"]
+    for p in paths:
+        assert np.load(p).dtype == np.float64

@@ -1,6 +1,8 @@
 """bench.py's N > 1 path end to end on a one-GPU box: two ranks launched exactly as the driver does
 (torch.distributed.run), both on device 0, sub-roots exchanged over gloo (STARKPERP_BENCH_SHARE_GPU=1,
-a hook that exists only for this test).  Checks the JSON contract and the combined root."""
+a hook that exists only for this test).  Checks the JSON contract and the combined root.  Also the plain one-GPU run
+(no --full) and what its --dump-outputs writes."""
+import functools
 import json
 import os
 import socket
@@ -37,7 +39,7 @@ def test_two_ranks_share_one_gpu(workload, extra, tmp_path):
                STARKPERP_BENCH_DETAIL=str(tmp_path / "detail.json"), STARKPERP_WINDOW_BITS="16")  # two ranks share one GPU here: small tables whatever the caller set
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--workload", workload, "--window-bits", "0", "--no-extras", "--no-cpu-baseline"] + extra
+           "--gpus", "2", "--workload", workload, "--window-bits", "0", "--no-extras", "--no-cpu-baseline", "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d, detail = _line_and_detail(out, str(tmp_path / "detail.json"))
@@ -75,7 +77,7 @@ def test_eight_ranks_share_one_gpu(workload, extra, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "8", "--workload", workload, "--window-bits", "0", "--no-extras", "--no-cpu-baseline",
-           "--no-airfri"] + extra  # (the per-rank AIR + FRI jobs of the default line are covered by the two-rank test)
+           "--no-airfri", "--full"] + extra  # (the per-rank AIR + FRI jobs of the default line are covered by the two-rank test)
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d, _ = _line_and_detail(out, str(tmp_path / "detail.json"))
@@ -99,7 +101,7 @@ def test_gpus_2_without_a_launcher_spawns_its_own_ranks(tmp_path):
                STARKPERP_BENCH_DETAIL=str(tmp_path / "detail.json"))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
            "--window-bits", "0", "--no-extras", "--no-cpu-baseline", "--no-airfri", "--min-timed-s", "0.3",
-           "--preheat-s", "0.2"]
+           "--preheat-s", "0.2", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d, detail = _line_and_detail(out, str(tmp_path / "detail.json"))
@@ -125,7 +127,7 @@ def test_default_line_is_a_sustained_measurement(tmp_path):
     held-clock roofline fraction; the 50 ms burst and the telemetry windows are in the detail file."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
            "--window-bits", "0", "--no-extras", "--no-cpu-baseline", "--no-airfri", "--min-timed-s", "1.0",
-           "--preheat-s", "0.5"]
+           "--preheat-s", "0.5", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["STARKPERP_BENCH_DETAIL"] = str(tmp_path / "detail.json")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -158,7 +160,7 @@ def test_default_line_with_every_leg_fits_the_bound(tmp_path):
     """The driver's own command shape (every leg on: CPU baselines, airfri, extras), shortened windows: the line the
     driver will parse - under 8 KB, roofline and cpu_baseline objects present, parity bits true, C3 as a distribution."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-           "--window-bits", "0", "--min-timed-s", "0.5", "--preheat-s", "0.3"]
+           "--window-bits", "0", "--min-timed-s", "0.5", "--preheat-s", "0.3", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["STARKPERP_BENCH_DETAIL"] = str(tmp_path / "detail.json")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
@@ -173,3 +175,52 @@ def test_default_line_with_every_leg_fits_the_bound(tmp_path):
     assert s["c3_one_call_ms"] > 0 and s["c3_one_call_ms_p90"] >= s["c3_one_call_ms"] >= s["c3_one_call_ms_min"]
     one = detail["extra"]["c3_4096_orders_one_call_seconds"]
     assert one["calls"] >= 20 and len(one["all"]) == one["calls"] and one["committed"] and one["all_verified"]
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_inner_nodes(t):
+    """Inner nodes (level 1 first, root last) of tree t of bench.py's seeded leaves on rank 0 - drawn for 64 trees, the
+    default --trees-per-call: tree t holds rows [t 2^16, (t + 1) 2^16) - recomputed by the C oracle."""
+    import torch
+    sys.path.insert(0, ROOT)
+    from benchlib.common import seeded_felts
+    from oracle import cref
+    limbs = seeded_felts(torch, 64 << 16, 1000, "cpu")[t << 16: (t + 1) << 16].numpy().astype("<i8").view("<u8")
+    leaves = [int(a) | int(b) << 64 | int(c) << 128 | int(e) << 192 for a, b, c, e in limbs.tolist()]
+    return [v for level in cref.merkle_levels(leaves)[1:] for v in level]
+
+
+@pytest.mark.parametrize("force_dist", [False, True])
+def test_plain_run_times_exactly_the_steps_and_dumps_the_last_tree(force_dist, tmp_path):
+    """A plain run (no --full): ONE line with the contract's keys from ONE region of exactly --steps steps, no detail
+    file, and --dump-outputs holds the last step's tree - which the C oracle recomputes from the same seeded leaves.
+    With --force-dist the same through a world-size-1 RCCL group (the sub-root combine after every call)."""
+    import numpy as np
+    steps, warmup = 5, 2
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--window-bits", "0", "--preheat-s", "0.2", "--dump-outputs", str(tmp_path / "out")]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env["STARKPERP_BENCH_DETAIL"] = str(tmp_path / "detail.json")
+    if force_dist:
+        cmd.append("--force-dist")
+        env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
+                   RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d, detail = _line_and_detail(out, str(tmp_path / "detail.json"))
+    assert out.stdout.strip().count("\n") == 0 and detail is None  # the line and nothing else
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
+        assert k in d, k
+    assert d["metric"] == "pedersen_hashes_per_sec" and d["unit"] == "hashes/s" and d["higher_is_better"] is True
+    assert d["steps"] == steps and d["warmup"] == warmup and d["timed"]["regions"] == 1
+    assert d["timed"]["preheat_s"] >= 0.2 and d["config"]["trees_in_timed_call"] == steps
+    assert d["value"] == pytest.approx(65535 * 1e3 / d["ms_per_step"], rel=1e-6)
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "airfri" not in d and "dist" not in d
+    nodes = np.load(tmp_path / "out" / "merkle_last_tree_inner_nodes.npy")
+    root = np.load(tmp_path / "out" / "merkle_last_tree_root.npy")
+    assert nodes.dtype == root.dtype == np.float64 and nodes.shape == (65535, 8) and root.shape == (1, 8)
+    want = _oracle_inner_nodes(steps - 1)
+    got = [sum(int(w) << (32 * j) for j, w in enumerate(row)) for row in nodes.tolist()]
+    assert got == want
+    assert sum(int(w) << (32 * j) for j, w in enumerate(root[0].tolist())) == want[-1]

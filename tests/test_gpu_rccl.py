@@ -94,7 +94,7 @@ def test_bench_force_dist_takes_the_multi_gpu_branches(workload, extra, tmp_path
     keeps what proves the process group (backend, world size, RCCL version, per-rank value, the combine check); the
     full report is in the detail file."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--workload", workload,
-           "--window-bits", "0", "--no-extras", "--no-cpu-baseline"] + extra
+           "--window-bits", "0", "--no-extras", "--no-cpu-baseline", "--full"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT,
                          env=_env(STARKPERP_WINDOW_BITS="16", STARKPERP_BENCH_DETAIL=str(tmp_path / "detail.json")))
     assert out.returncode == 0, out.stderr[-3000:]

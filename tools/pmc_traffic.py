@@ -8,9 +8,9 @@ bench.py prints `traffic` from that file and says whether its own run has the sa
 Run on the GPU box:
 
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -o b -- python bench.py --no-cpu-baseline --no-extras
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -o b -- python bench.py --no-cpu-baseline --no-extras
-  python tools/pmc_traffic.py gpurun_out/pmc_fetch/b_counter_collection.csv gpurun_out/pmc_write/b_counter_collection.csv
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out/pmc_fetch -o b -- python bench.py --full --no-cpu-baseline --no-extras
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d out/pmc_write -o b -- python bench.py --full --no-cpu-baseline --no-extras
+  python tools/pmc_traffic.py out/pmc_fetch/b_counter_collection.csv out/pmc_write/b_counter_collection.csv
 
 Units (MI355X_MICROARCH.md, HBM section): FETCH_SIZE / WRITE_SIZE are in KiB.  The guide's gfx950
 note (FETCH_SIZE reads half the bytes of a WIDE COALESCED stream) does not apply to these kernels,

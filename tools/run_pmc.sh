@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 R=$PWD
 O=$R/gpurun_out/r02prof
 mkdir -p $O
-CMD="python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-airfri"
+CMD="python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras --no-airfri"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- $CMD > $O/stats_bench.json 2> $O/stats.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o b -- $CMD > $O/fetch_bench.json 2> $O/fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -o b -- $CMD > $O/write_bench.json 2> $O/write.err

@@ -16,7 +16,7 @@ note() { echo "[r06prof +$((SECONDS - T0))s] $*" | tee -a $O/log.txt; }
 
 # ---- 1. kernel trace + stats of the driver's own command --------------------------------------------------------
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 \
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full \
     > $O/r06_stats_bench.json 2> $O/stats.err
 cd $R
 cp bench_detail.json $O/r06_stats_bench_detail.json
@@ -27,12 +27,12 @@ cp $KS $O/r06_kernel_stats.csv
 note "kernel stats done ($NL timed launches)"
 
 # ---- 2. the same command without a profiler: the line and the detail the judge compares with the driver's -------
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_default.json 2> $O/bench_default.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r06_bench_default.json 2> $O/bench_default.err
 cp bench_detail.json $O/r06_bench_detail.json
 note "plain bench done: $(wc -c < $O/r06_bench_default.json) bytes"
 
 # ---- 3. PMC traffic, merkle workload (separate FETCH_SIZE / WRITE_SIZE passes; shorter windows: counters serialise) --
-CMD="python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-airfri --min-timed-s 0.25 --preheat-s 0.25"
+CMD="python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras --no-airfri --min-timed-s 0.25 --preheat-s 0.25"
 cd /tmp
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -o b -- $CMD > $O/fetch_bench.json 2> $O/fetch.err
 cp $R/bench_detail.json $O/fetch_detail.json
@@ -41,7 +41,7 @@ cd $R
 NLF=$(python -c "import json;print(json.load(open('$O/fetch_bench.json'))['roofline']['launches'])")
 KEY=$(python -c "import json;d=json.load(open('$O/fetch_detail.json'));c=d['config'];print('merkle:steps=%d:calls=%s:streams=%d:w=%d'%(d['steps'],','.join(map(str,c['timed_calls'])),c['streams'],c['window_bits']))")
 FC=$(find $O/fetch -name "*counter_collection.csv" | head -1); WC=$(find $O/write -name "*counter_collection.csv" | head -1)
-PMC_TIMED_LAUNCHES=$NLF python tools/pmc_traffic.py $FC $WC r06_pmc_traffic.json "$KEY" "bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-airfri --min-timed-s 0.25 --preheat-s 0.25 (round 6 evidence pass: the sustained line with shorter windows - PMC passes serialise the dispatches; the pure ped_accumulate_kernel launches are levels 0 and 1 of every 20-tree forest), 26-bit windows" > /dev/null
+PMC_TIMED_LAUNCHES=$NLF python tools/pmc_traffic.py $FC $WC r06_pmc_traffic.json "$KEY" "bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras --no-airfri --min-timed-s 0.25 --preheat-s 0.25 (round 6 evidence pass: the sustained line with shorter windows - PMC passes serialise the dispatches; the pure ped_accumulate_kernel launches are levels 0 and 1 of every 20-tree forest), 26-bit windows" > /dev/null
 cp profiles/r06_pmc_traffic.json $O/
 note "merkle PMC traffic done (key $KEY)"
 
@@ -85,7 +85,7 @@ note "C3 done"
 
 # ---- 8. with the new instruction counts / traffic files in place: the line once more (what bench.py prints from them) --
 cp $O/r06_valu_issue.json $O/r06_pmc_traffic.json $O/r06_pmc_traffic_airfri.json $O/r06_c3_sq_counters.json profiles/
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_default.json 2> $O/bench_default.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r06_bench_default.json 2> $O/bench_default.err
 cp bench_detail.json $O/r06_bench_detail.json
 note "final line: $(wc -c < $O/r06_bench_default.json) bytes"
 rm -rf $O/stats $O/fetch $O/write $O/afetch $O/awrite $O/astats $O/sq26 $O/sq21 $O/lc $O/lt
