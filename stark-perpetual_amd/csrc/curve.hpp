@@ -33,89 +33,144 @@ SP_HD xyzz xyzz_from_aff(const aff& p) {
   return r;
 }
 
+// The five XYZZ additions below take the form of their field multiplications as a template argument: SCAN = true
+// is the product-scanning form of fp29.hpp (no separate carry additions, each multiplication one dependent chain),
+// for kernels that have other waves to issue from; the default is the column form.  Both give the same limbs.
+// The three additions of the one-lane bulk body (madd, madd_x_only, mmadd) scan the multiplications that do not
+// depend on each other in groups of two or three (fe_scan), so that a lane always has two chains in flight.
 // acc + q, q affine ("madd-2008-s").  Exceptional inputs (acc == +-q, acc == infinity) are not
 // handled here: they drive ZZ to 0, which stays 0 through later additions and is detected by the
 // caller on the final ZZ.  Call sites argue why they are unreachable.
+template <bool SCAN = false>
 SP_HD xyzz xyzz_madd(const xyzz& a, const aff& q) {
-  const fe U2 = fe_mul(q.x, a.ZZ);           // N
-  const fe S2 = fe_mul(q.y, a.ZZZ);          // N
+  if constexpr (SCAN && SP_FE_SCAN) {
+    fe t[3];
+    fe_scan(t, scan_mul{q.x, a.ZZ}, scan_mul{q.y, a.ZZZ});  // U2, S2
+    const fe P = fe_sub(t[0], a.X), R = fe_sub(t[1], a.Y);
+    const fe P2 = fe_dbl(P), R2 = fe_dbl(R);
+    fe_scan(t, scan_sqr{P, P2}, scan_sqr{R, R2});
+    const fe PP = t[0], RR = t[1];
+    fe_scan(t, scan_mul{P, PP}, scan_mul{a.X, PP});
+    const fe PPP = t[0], Q = t[1];
+    xyzz r;
+    r.X = fe_carry(fe_sub(fe_sub(RR, PPP), fe_dbl(Q)));
+    const fe D = fe_sub(Q, r.X), nY = fe_neg_pinned(a.Y);
+    fe_scan(t, scan_mul2{R, D, nY, PPP}, scan_mul{a.ZZ, PP}, scan_mul{a.ZZZ, PPP});
+    r.Y = t[0];
+    r.ZZ = t[1];
+    r.ZZZ = t[2];
+    return r;
+  }
+  const fe U2 = fe_mul_t<SCAN>(q.x, a.ZZ);           // N
+  const fe S2 = fe_mul_t<SCAN>(q.y, a.ZZZ);          // N
   const fe P = fe_sub(U2, a.X);              // B=1 (signed)
   const fe R = fe_sub(S2, a.Y);              // B=1
-  const fe PP = fe_sqr(P);                   // cols < 9*2^58
-  const fe PPP = fe_mul(P, PP);
-  const fe Q = fe_mul(a.X, PP);
+  const fe PP = fe_sqr_t<SCAN>(P);                   // cols < 9*2^58
+  const fe PPP = fe_mul_t<SCAN>(P, PP);
+  const fe Q = fe_mul_t<SCAN>(a.X, PP);
   xyzz r;
   // X3 = R^2 - PPP - 2Q : limbs in (-3*2^29, 2^29) -> carry to N
-  r.X = fe_carry(fe_sub(fe_sub(fe_sqr(R), PPP), fe_dbl(Q)));
+  r.X = fe_carry(fe_sub(fe_sub(fe_sqr_t<SCAN>(R), PPP), fe_dbl(Q)));
   // Y3 = R (Q - X3) - Y1 PPP : both products share one reduction, cols < 9*2^58 + 9*2^58
-  r.Y = fe_mul_sub_mul(R, fe_sub(Q, r.X), a.Y, PPP);
-  r.ZZ = fe_mul(a.ZZ, PP);
-  r.ZZZ = fe_mul(a.ZZZ, PPP);
+  r.Y = fe_mul_sub_mul_t<SCAN>(R, fe_sub(Q, r.X), a.Y, PPP);
+  r.ZZ = fe_mul_t<SCAN>(a.ZZ, PP);
+  r.ZZZ = fe_mul_t<SCAN>(a.ZZZ, PPP);
   return r;
 }
 
 // Last addition of a chain when only x = X/ZZ is wanted: skips Y3 and ZZZ3 (saves 3M).
+template <bool SCAN = false>
 SP_HD void xyzz_madd_x_only(const xyzz& a, const aff& q, fe& X3, fe& ZZ3) {
-  const fe U2 = fe_mul(q.x, a.ZZ);
-  const fe S2 = fe_mul(q.y, a.ZZZ);
+  if constexpr (SCAN && SP_FE_SCAN) {
+    fe t[3];
+    fe_scan(t, scan_mul{q.x, a.ZZ}, scan_mul{q.y, a.ZZZ});
+    const fe P = fe_sub(t[0], a.X), R = fe_sub(t[1], a.Y);
+    const fe P2 = fe_dbl(P), R2 = fe_dbl(R);
+    fe_scan(t, scan_sqr{P, P2}, scan_sqr{R, R2});
+    const fe PP = t[0], RR = t[1];
+    fe_scan(t, scan_mul{P, PP}, scan_mul{a.X, PP}, scan_mul{a.ZZ, PP});
+    X3 = fe_carry(fe_sub(fe_sub(RR, t[0]), fe_dbl(t[1])));
+    ZZ3 = t[2];
+    return;
+  }
+  const fe U2 = fe_mul_t<SCAN>(q.x, a.ZZ);
+  const fe S2 = fe_mul_t<SCAN>(q.y, a.ZZZ);
   const fe P = fe_sub(U2, a.X);
   const fe R = fe_sub(S2, a.Y);
-  const fe PP = fe_sqr(P);
-  const fe PPP = fe_mul(P, PP);
-  const fe Q = fe_mul(a.X, PP);
-  X3 = fe_carry(fe_sub(fe_sub(fe_sqr(R), PPP), fe_dbl(Q)));
-  ZZ3 = fe_mul(a.ZZ, PP);
+  const fe PP = fe_sqr_t<SCAN>(P);
+  const fe PPP = fe_mul_t<SCAN>(P, PP);
+  const fe Q = fe_mul_t<SCAN>(a.X, PP);
+  X3 = fe_carry(fe_sub(fe_sub(fe_sqr_t<SCAN>(R), PPP), fe_dbl(Q)));
+  ZZ3 = fe_mul_t<SCAN>(a.ZZ, PP);
 }
 
 // Sum of two affine points -> XYZZ ("mmadd-2008-s", 4M + 2S).
+template <bool SCAN = false>
 SP_HD xyzz xyzz_mmadd(const aff& a, const aff& b) {
+  if constexpr (SCAN && SP_FE_SCAN) {
+    const fe P = fe_sub(b.x, a.x), R = fe_carry(fe_sub(b.y, a.y));  // see below
+    const fe P2 = fe_dbl(P), R2 = fe_dbl(R);
+    fe t[2];
+    fe_scan(t, scan_sqr{P, P2}, scan_sqr{R, R2});
+    const fe PP = t[0], RR = t[1];
+    fe_scan(t, scan_mul{P, PP}, scan_mul{a.x, PP});
+    const fe PPP = t[0], Q = t[1];
+    xyzz r;
+    r.X = fe_carry(fe_sub(fe_sub(RR, PPP), fe_dbl(Q)));
+    r.Y = fe_mul_sub_mul_scan(R, fe_sub(Q, r.X), a.y, PPP);
+    r.ZZ = PP;
+    r.ZZZ = PPP;
+    return r;
+  }
   const fe P = fe_sub(b.x, a.x);
   // callers pass table entries whose y may be negated (signed windows): b.y - a.y can reach B = 2 and
   // nine maximal products of its square would exceed the 64-bit column budget - carry it to N
   const fe R = fe_carry(fe_sub(b.y, a.y));
-  const fe PP = fe_sqr(P);
-  const fe PPP = fe_mul(P, PP);
-  const fe Q = fe_mul(a.x, PP);
+  const fe PP = fe_sqr_t<SCAN>(P);
+  const fe PPP = fe_mul_t<SCAN>(P, PP);
+  const fe Q = fe_mul_t<SCAN>(a.x, PP);
   xyzz r;
-  r.X = fe_carry(fe_sub(fe_sub(fe_sqr(R), PPP), fe_dbl(Q)));
-  r.Y = fe_mul_sub_mul(R, fe_sub(Q, r.X), a.y, PPP);
+  r.X = fe_carry(fe_sub(fe_sub(fe_sqr_t<SCAN>(R), PPP), fe_dbl(Q)));
+  r.Y = fe_mul_sub_mul_t<SCAN>(R, fe_sub(Q, r.X), a.y, PPP);
   r.ZZ = PP;
   r.ZZZ = PPP;
   return r;
 }
 
 // General XYZZ + XYZZ ("add-2008-s", 12M + 2S); used for cross-lane combines.
+template <bool SCAN = false>
 SP_HD xyzz xyzz_add(const xyzz& a, const xyzz& b) {
-  const fe U1 = fe_mul(a.X, b.ZZ);
-  const fe U2 = fe_mul(b.X, a.ZZ);
-  const fe S1 = fe_mul(a.Y, b.ZZZ);
-  const fe S2 = fe_mul(b.Y, a.ZZZ);
+  const fe U1 = fe_mul_t<SCAN>(a.X, b.ZZ);
+  const fe U2 = fe_mul_t<SCAN>(b.X, a.ZZ);
+  const fe S1 = fe_mul_t<SCAN>(a.Y, b.ZZZ);
+  const fe S2 = fe_mul_t<SCAN>(b.Y, a.ZZZ);
   const fe P = fe_sub(U2, U1);
   const fe R = fe_sub(S2, S1);
-  const fe PP = fe_sqr(P);
-  const fe PPP = fe_mul(P, PP);
-  const fe Q = fe_mul(U1, PP);
+  const fe PP = fe_sqr_t<SCAN>(P);
+  const fe PPP = fe_mul_t<SCAN>(P, PP);
+  const fe Q = fe_mul_t<SCAN>(U1, PP);
   xyzz r;
-  r.X = fe_carry(fe_sub(fe_sub(fe_sqr(R), PPP), fe_dbl(Q)));
-  r.Y = fe_mul_sub_mul(R, fe_sub(Q, r.X), S1, PPP);
-  r.ZZ = fe_mul(fe_mul(a.ZZ, b.ZZ), PP);
-  r.ZZZ = fe_mul(fe_mul(a.ZZZ, b.ZZZ), PPP);
+  r.X = fe_carry(fe_sub(fe_sub(fe_sqr_t<SCAN>(R), PPP), fe_dbl(Q)));
+  r.Y = fe_mul_sub_mul_t<SCAN>(R, fe_sub(Q, r.X), S1, PPP);
+  r.ZZ = fe_mul_t<SCAN>(fe_mul_t<SCAN>(a.ZZ, b.ZZ), PP);
+  r.ZZZ = fe_mul_t<SCAN>(fe_mul_t<SCAN>(a.ZZZ, b.ZZZ), PPP);
   return r;
 }
 
 // Last combine of a butterfly when only x = X/ZZ is wanted: skips Y3 and ZZZ3 (saves 5M).
+template <bool SCAN = false>
 SP_HD void xyzz_add_x_only(const xyzz& a, const xyzz& b, fe& X3, fe& ZZ3) {
-  const fe U1 = fe_mul(a.X, b.ZZ);
-  const fe U2 = fe_mul(b.X, a.ZZ);
-  const fe S1 = fe_mul(a.Y, b.ZZZ);
-  const fe S2 = fe_mul(b.Y, a.ZZZ);
+  const fe U1 = fe_mul_t<SCAN>(a.X, b.ZZ);
+  const fe U2 = fe_mul_t<SCAN>(b.X, a.ZZ);
+  const fe S1 = fe_mul_t<SCAN>(a.Y, b.ZZZ);
+  const fe S2 = fe_mul_t<SCAN>(b.Y, a.ZZZ);
   const fe P = fe_sub(U2, U1);
   const fe R = fe_sub(S2, S1);
-  const fe PP = fe_sqr(P);
-  const fe PPP = fe_mul(P, PP);
-  const fe Q = fe_mul(U1, PP);
-  X3 = fe_carry(fe_sub(fe_sub(fe_sqr(R), PPP), fe_dbl(Q)));
-  ZZ3 = fe_mul(fe_mul(a.ZZ, b.ZZ), PP);
+  const fe PP = fe_sqr_t<SCAN>(P);
+  const fe PPP = fe_mul_t<SCAN>(P, PP);
+  const fe Q = fe_mul_t<SCAN>(U1, PP);
+  X3 = fe_carry(fe_sub(fe_sub(fe_sqr_t<SCAN>(R), PPP), fe_dbl(Q)));
+  ZZ3 = fe_mul_t<SCAN>(fe_mul_t<SCAN>(a.ZZ, b.ZZ), PP);
 }
 
 // ---- Jacobian, general curve coefficient a (Montgomery form) ----

@@ -22,6 +22,7 @@
 // the product library only ever runs it on the device (plus one-off table seeds at sp_init).
 #pragma once
 #include <stdint.h>
+#include <utility>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -315,6 +316,193 @@ SP_HD fe fe_mul3_add(const fe& a, const fe& b, const fe& c, const fe& d, const f
   cols_mac(t, c, d);
   cols_mac(t, e, f);
   return fe_reduce(t);
+}
+
+// ---- product scanning: the same results, column by column -------------------------------------------
+// fe_reduce hands a column's carry on with a 64-bit addition of its own (t.c[i + 1] += t.c[i] >> LB, and
+// v = t.c[9 + k] + carry in the last pass): 15 v_lshl_add_u64 per multiplication at the issue cost of a
+// multiply-add each.  v_mad_i64_i32 already has a 64-bit addend, so a column whose chain STARTS from the carry
+// of the column before it needs no such addition.  For column c = 0 .. 16:
+//     acc = carry;  acc += the column's products;  acc += q[c - 6] (-P6);  acc += q[c - 8] (-P8);
+//     c <= 8: q[c] = acc & LMASK     c >= 9: r.l[c - 9] = acc & LMASK     carry = acc >> LB;    r.l[8] = last carry
+// Every column holds the same integer as in fe_reduce when its low 29 bits are taken, so the result is the
+// same limb for limb (tests/test_field_scan_host.py).  Writing it this way in plain C++ is NOT enough: LLVM
+// reassociates the sum so that the carry, which hangs off the whole previous chain, is added last - the
+// identical instruction histogram.  scan_pin after every step keeps the order (the 64-bit form of fe_pin).
+// Bounds: a carry is below 2^63 / 2^29 = 2^34 in magnitude, so a column's running sum exceeds the sum of its
+// own terms (products < 2^63 as stated at the call sites, reduction terms < 2^29 (P6 + P8) < 2^53) by less
+// than 2^35; every step is checked on the host (SP_CHK64).
+// The price is a dependent chain through all 99 multiply-adds of a multiplication, and the compiler does not
+// interleave two such chains by itself (measured: 1 638 of the bulk kernel's 1 989 multiply-adds directly behind the
+// one they depend on, and no gain in time from 10 % fewer instructions, profiles/fe_scan_ab.txt).  So the scan runs
+// over SEVERAL independent multiplications at once (fe_scan: the chains of a group advance one step each in turn),
+// and the group law hands it the multiplications of an addition that do not depend on each other, two or three at
+// a time (curve.hpp).
+SP_HD void scan_pin(int64_t& acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(acc));
+#else
+  (void)acc;
+#endif
+}
+// acc += a * b, kept as ONE multiply-add whose addend is acc
+SP_HD void scan_mac(int64_t& acc, int32_t a, int32_t b) {
+  SP_CHK64((__int128)acc + (__int128)a * b);
+  acc += (int64_t)a * (int64_t)b;
+  scan_pin(acc);
+}
+// -a with pinned limbs: a subtracted product multiplies by the negated limb, so its step stays one multiply-add
+// (acc -= a * b under a pin becomes a v_sub_co / v_subb_co pair behind a multiplication)
+SP_HD fe fe_neg_pinned(const fe& a) {
+  fe r = fe_neg(a);
+  fe_pin(r);
+  return r;
+}
+// One chain = one sum of products with its own reduction.  step(c, i, acc) does the i-th accumulate step of
+// column c, i < STEPS, or nothing when that column has no such step.
+struct scan_mul {  // a b
+  static constexpr int STEPS = NL;
+  const fe &a, &b;
+  SP_HD void step(int c, int i, int64_t& acc) const {
+    const int j = c - i;
+    if (j >= 0 && j < NL) scan_mac(acc, a.l[i], b.l[j]);
+  }
+};
+struct scan_sqr {  // a a with d = 2 a (limb-wise): 45 products
+  static constexpr int STEPS = NL;
+  const fe &a, &d;
+  SP_HD void step(int c, int i, int64_t& acc) const {
+    const int j = c - i;
+    if (j > i && j < NL) scan_mac(acc, d.l[i], a.l[j]);
+    if (j == i) scan_mac(acc, a.l[i], a.l[i]);
+  }
+};
+struct scan_mul2 {  // a b + c d (for a b - c d pass fe_neg_pinned(c))
+  static constexpr int STEPS = 2 * NL;
+  const fe &a, &b, &c, &d;
+  SP_HD void step(int k, int i, int64_t& acc) const {
+    const int j = k - (i % NL);
+    if (j >= 0 && j < NL) scan_mac(acc, i < NL ? a.l[i] : c.l[i - NL], i < NL ? b.l[j] : d.l[j]);
+  }
+};
+struct scan_mul3 {  // a b + c d + e f
+  static constexpr int STEPS = 3 * NL;
+  const fe &a, &b, &c, &d, &e, &f;
+  SP_HD void step(int k, int i, int64_t& acc) const {
+    const int j = k - (i % NL);
+    if (j >= 0 && j < NL)
+      scan_mac(acc, i < NL ? a.l[i] : i < 2 * NL ? c.l[i - NL] : e.l[i - 2 * NL], i < NL ? b.l[j] : i < 2 * NL ? d.l[j] : f.l[j]);
+  }
+};
+// The scan is expanded by templates, not by loops: the unrolled body of three chains is larger than what
+// "#pragma unroll" is allowed to produce, and a loop that stays a loop indexes q[] and r[] in scratch memory.
+template <int N>
+struct scan_state {
+  int64_t acc[N];    // running column sum of each chain
+  int32_t q[N][NL];  // its quotient limbs
+  int32_t np6, np8;
+};
+constexpr int scan_max(int a) { return a; }
+template <class... T>
+constexpr int scan_max(int a, T... rest) { return a > scan_max(rest...) ? a : scan_max(rest...); }
+// step I of column COL on every chain that has one
+template <int COL, int I, int N, class... C>
+SP_HD void scan_round(scan_state<N>& s, const C&... chains) {
+  int k = 0;
+  ((I < C::STEPS ? chains.step(COL, I, s.acc[k]) : (void)0, ++k), ...);
+}
+template <int COL, int N, class... C, int... I>
+SP_HD void scan_column(scan_state<N>& s, fe* r, std::integer_sequence<int, I...>, const C&... chains) {
+  (scan_round<COL, I>(s, chains...), ...);
+  if constexpr (COL >= 6 && COL - 6 < NL) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) scan_mac(s.acc[k], s.q[k][COL - 6], s.np6);
+  }
+  if constexpr (COL >= 8) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) scan_mac(s.acc[k], s.q[k][COL - 8], s.np8);
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const int32_t lo = (int32_t)((uint32_t)s.acc[k] & LMASK);
+    if constexpr (COL < NL) s.q[k][COL] = lo; else r[k].l[COL - NL] = lo;
+    s.acc[k] >>= LB;  // arithmetic shift = floor
+  }
+}
+template <int N, class... C, int... COL>
+SP_HD void scan_columns(scan_state<N>& s, fe* r, std::integer_sequence<int, COL...>, const C&... chains) {
+  (scan_column<COL>(s, r, std::make_integer_sequence<int, scan_max(C::STEPS...)>(), chains...), ...);
+}
+// r[k] = reduced sum of chain k.  The chains advance in turn, one accumulate step each.
+template <class... C>
+SP_HD void fe_scan(fe* r, const C&... chains) {
+  constexpr int N = sizeof...(C);
+  scan_state<N> s;
+  s.np6 = -P6;
+  s.np8 = -P8;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+s"(s.np6), "+s"(s.np8));  // SGPR multiplicands, as in fe_reduce
+#endif
+#pragma unroll
+  for (int k = 0; k < N; ++k) s.acc[k] = 0;
+  scan_columns(s, r, std::make_integer_sequence<int, 17>(), chains...);
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    SP_CHK32(s.acc[k]);
+    r[k].l[8] = (int32_t)s.acc[k];
+    fe_pin(r[k]);
+  }
+}
+SP_HD fe fe_mul_scan(const fe& a, const fe& b) {
+  fe r;
+  fe_scan(&r, scan_mul{a, b});
+  return r;
+}
+SP_HD fe fe_sqr_scan(const fe& a) {
+  const fe d = fe_dbl(a);
+  fe r;
+  fe_scan(&r, scan_sqr{a, d});
+  return r;
+}
+// a*b - c*d with a single reduction
+SP_HD fe fe_mul_sub_mul_scan(const fe& a, const fe& b, const fe& c, const fe& d) {
+  const fe nc = fe_neg_pinned(c);
+  fe r;
+  fe_scan(&r, scan_mul2{a, b, nc, d});
+  return r;
+}
+// a*b + c*d with a single reduction
+SP_HD fe fe_mul_add_mul_scan(const fe& a, const fe& b, const fe& c, const fe& d) {
+  fe r;
+  fe_scan(&r, scan_mul2{a, b, c, d});
+  return r;
+}
+// a*b + c*d + e*f with a single reduction
+SP_HD fe fe_mul3_add_scan(const fe& a, const fe& b, const fe& c, const fe& d, const fe& e, const fe& f) {
+  fe r;
+  fe_scan(&r, scan_mul3{a, b, c, d, e, f});
+  return r;
+}
+
+// Which form a kernel family uses is a template argument of the group law (curve.hpp); SP_FE_SCAN=0 builds a
+// library whose kernels use the column forms everywhere (the A/B partner, make VARIANT=.. EXTRA=-DSP_FE_SCAN=0).
+#ifndef SP_FE_SCAN
+#define SP_FE_SCAN 1
+#endif
+template <bool SCAN>
+SP_HD fe fe_mul_t(const fe& a, const fe& b) {
+  if constexpr (SCAN && SP_FE_SCAN) return fe_mul_scan(a, b);
+  else return fe_mul(a, b);
+}
+template <bool SCAN>
+SP_HD fe fe_sqr_t(const fe& a) {
+  if constexpr (SCAN && SP_FE_SCAN) return fe_sqr_scan(a);
+  else return fe_sqr(a);
+}
+template <bool SCAN>
+SP_HD fe fe_mul_sub_mul_t(const fe& a, const fe& b, const fe& c, const fe& d) {
+  if constexpr (SCAN && SP_FE_SCAN) return fe_mul_sub_mul_scan(a, b, c, d);
+  else return fe_mul_sub_mul(a, b, c, d);
 }
 
 // ---- canonical form ----

@@ -132,6 +132,18 @@ __device__ __forceinline__ void operand_pointers(const uint64_t* x, const uint64
   }
 }
 
+// Form of the field multiplications per kernel family (fp29.hpp "product scanning", curve.hpp): the scanning form
+// removes the 64-bit carry additions of a reduction and makes a multiplication one dependent chain.  The one-lane
+// bulk body runs three waves per SIMD and is bound by VALU issue, so it takes the scanning form; the lane-split
+// body is latency-bound (one dependent instruction costs 2.5 - 3.75 ns there) and keeps the column form unless a
+// measurement says otherwise (profiles/fe_scan_ab.txt).  -DSP_FE_SCAN=0 switches every family back.
+#ifndef SP_SCAN_BULK
+#define SP_SCAN_BULK true
+#endif
+#ifndef SP_SCAN_SPLIT
+#define SP_SCAN_SPLIT false
+#endif
+
 // Kernel A: one hash per thread -> projective (X, ZZ) in scratch.  `e` = the thread's hash.
 __device__ __forceinline__ void
 bulk_accumulate(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, size_t xstride,
@@ -178,7 +190,7 @@ bulk_accumulate(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, 
       n2 = ld_raw(r.entry);
       neg2 = r.negative;
     }
-    acc = xyzz_mmadd(unpack_raw(e0), q1);
+    acc = xyzz_mmadd<SP_SCAN_BULK>(unpack_raw(e0), q1);
     first = 2;
   } else {
     acc = xyzz_from_aff(unpack_raw(e0));
@@ -192,12 +204,12 @@ bulk_accumulate(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, 
       n2 = ld_raw(r.entry);
       neg2 = r.negative;
     }
-    acc = xyzz_madd(acc, q);
+    acc = xyzz_madd<SP_SCAN_BULK>(acc, q);
   }
   if (nwin > 1) {
     // only x = X / ZZ of the result is wanted: the last addition skips Y3 and ZZZ3 (3 of 10 multiplications)
     fe X3, ZZ3;
-    xyzz_madd_x_only(acc, signed_aff(n1, neg1), X3, ZZ3);
+    xyzz_madd_x_only<SP_SCAN_BULK>(acc, signed_aff(n1, neg1), X3, ZZ3);
     store_limbs(sX, plane, e, X3);
     store_limbs(sZZ, plane, e, ZZ3);
   } else {
@@ -277,7 +289,7 @@ __device__ __forceinline__ xyzz split_accumulate(const uint64_t* fx, const uint6
       rn = entry(g0 + 2);
       nxt = ld_raw(rn.entry);
     }
-    acc = xyzz_mmadd(q0, q1);
+    acc = xyzz_mmadd<SP_SCAN_SPLIT>(q0, q1);
   }
   for (int j = 2; j < cnt; ++j) {
     const aff q = signed_aff(nxt, rn.negative);
@@ -285,7 +297,7 @@ __device__ __forceinline__ xyzz split_accumulate(const uint64_t* fx, const uint6
       rn = entry(g0 + j + 1);
       nxt = ld_raw(rn.entry);
     }
-    acc = xyzz_madd(acc, q);
+    acc = xyzz_madd<SP_SCAN_SPLIT>(acc, q);
   }
   // NOT unrolled on purpose: one copy of the 14-multiplication general addition keeps the kernel
   // inside the instruction cache (a 58 KB straight-line body ran 2x slower than a 25 KB loop).
@@ -296,7 +308,7 @@ __device__ __forceinline__ xyzz split_accumulate(const uint64_t* fx, const uint6
     o.Y = shfl_xor_fe(acc.Y, 1 << r);
     o.ZZ = shfl_xor_fe(acc.ZZ, 1 << r);
     o.ZZZ = shfl_xor_fe(acc.ZZZ, 1 << r);
-    acc = xyzz_add(acc, o);
+    acc = xyzz_add<SP_SCAN_SPLIT>(acc, o);
   }
   if constexpr (LOG_L > 0) {  // last round: only x = X / ZZ of the total is wanted (Y, ZZZ are left stale)
     constexpr int r = LOG_L - 1;
@@ -306,7 +318,7 @@ __device__ __forceinline__ xyzz split_accumulate(const uint64_t* fx, const uint6
     o.ZZ = shfl_xor_fe(acc.ZZ, 1 << r);
     o.ZZZ = shfl_xor_fe(acc.ZZZ, 1 << r);
     fe X3, ZZ3;
-    xyzz_add_x_only(acc, o, X3, ZZ3);
+    xyzz_add_x_only<SP_SCAN_SPLIT>(acc, o, X3, ZZ3);
     acc.X = X3;
     acc.ZZ = ZZ3;
   }

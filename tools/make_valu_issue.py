@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""profiles/r06_valu_issue.json: the per-hash SQ_INSTS_VALU counts of THIS round's binary on top of the issue-interval
-model of round 4 (the opcode mix of ped_accumulate_kernel and the per-opcode intervals did not change: csrc/pedersen.hip's
-accumulate body is the one profiles/r04_valu_issue.json priced).
+"""profiles/r06_valu_issue.json: the per-hash SQ_INSTS_VALU counts of THIS binary on top of the issue-interval model
+of round 4.  The per-opcode intervals are round 4's (profiles/r04_valu_rate_ubench.txt); the opcode MIX of
+ped_accumulate_kernel is the static histogram of the shipped kernel (tools/valu_mix.py, profiles/fe_scan_valu_mix.json):
+the product-scanning field multiplication (csrc/fp29.hpp) took the 64-bit carry additions out of it, so the mix of
+round 4 (349 v_lshl_add_u64 in 3 911 instructions) no longer describes the stream.
 
-    python tools/make_valu_issue.py <counts_w26.json> <counts_w21.json> <level_counters.txt> <evidence.json> > r06_valu_issue.json
+    python tools/valu_mix.py profiles/r04_valu_rate_ubench.txt > profiles/fe_scan_valu_mix.json     # needs hipcc only
+    python tools/make_valu_issue.py <counts_w26.json> <counts_w21.json> <level_counters.txt> <evidence.json> [mix.json] > r06_valu_issue.json
 
 counts_*.json: tools/valu_counts.py on a `--pmc SQ_INSTS_VALU SQ_WAVES GRBM_GUI_ACTIVE` pass of tools/bulk_only.py 22 <w>;
 level_counters.txt: tools/level_counters.py on the 20-tree forest (the finish-lds launches the bulk batch never takes)."""
@@ -20,12 +23,25 @@ def main():
     w26, w21 = json.load(open(sys.argv[1])), json.load(open(sys.argv[2]))
     ev = json.load(open(sys.argv[4]))
     out = dict(base)
-    out["_source"] = ("round 6, tools/run_r06_prof.sh on the end-of-round binary (lib sha256 %s..., csrc sha256 %s...).  Counts: "
+    mix_path = sys.argv[5] if len(sys.argv) > 5 else os.path.join(ROOT, "profiles", "fe_scan_valu_mix.json")
+    mix = json.load(open(mix_path))
+    out["mix"] = dict(base["mix"])
+    out["mix"].update({k: mix[k] for k in ("static_valu_instructions", "histogram", "cycles_per_instr_mix_at_2_waves_per_simd",
+                                           "cycles_per_instr_mix_at_8_waves_per_simd",
+                                           "cycles_per_instr_mix_best_of_any_occupancy")})
+    total = float(mix["static_valu_instructions"])
+    four = sum(n for op, n in mix["histogram"].items() if mix["priced_as"][op]["cycles_at_8_waves"] >= 3.5)
+    out["mix"]["share_of_four_cycle_opcodes"] = round(four / total, 3)
+    out["mix"]["share_of_multiply_adds"] = round((mix["histogram"].get("v_mad_i64_i32", 0) + mix["histogram"].get("v_mad_u64_u32", 0)) / total, 3)
+    out["cycles_per_wave64_valu_instr"] = mix["cycles_per_instr_mix_best_of_any_occupancy"]
+    out["_source"] = ("evidence pass on the shipped binary (lib sha256 %s..., csrc sha256 %s...).  Counts: "
                       "rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES GRBM_GUI_ACTIVE --kernel-trace -- python tools/bulk_only.py 22 26 "
-                      "(and 22 21), tools/valu_counts.py.  Issue interval (cycles_per_wave64_valu_instr, mix): carried over from "
-                      "profiles/r04_valu_issue.json - the accumulate kernel's opcode mix and the per-opcode intervals "
-                      "(profiles/r04_valu_rate_ubench.txt) are unchanged.  27-bit entry: carried over, not re-measured."
-                      % (ev["lib_sha256"][:16], ev["csrc_sha256"][:16]))
+                      "(and 22 21), tools/valu_counts.py.  Issue interval (cycles_per_wave64_valu_instr, mix): the static "
+                      "histogram of the shipped ped_accumulate_kernel (tools/valu_mix.py -> profiles/%s: %d VALU instructions, "
+                      "%d v_lshl_add_u64) priced with the per-opcode intervals of profiles/r04_valu_rate_ubench.txt.  "
+                      "mix_finish_kernel and the 27-bit entry: carried over, not re-measured."
+                      % (ev["lib_sha256"][:16], ev["csrc_sha256"][:16], os.path.basename(mix_path),
+                         mix["static_valu_instructions"], mix["histogram"].get("v_lshl_add_u64", 0)))
     for w, m in (("26", w26), ("21", w21)):
         e = dict(base["window_bits"].get(w, {}))
         e["accumulate_instr_per_hash"] = m["accumulate_instr_per_hash"]
