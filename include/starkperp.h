@@ -23,6 +23,7 @@
  *     serialises the host-side bookkeeping; scratch, window tables of the verifier and NTT work
  *     columns are per stream, so _dev calls on different streams overlap on the device.  The
  *     host-pointer batches that carry no shared state - sp_pedersen_batch, sp_pedersen_chains,
+ *     sp_pedersen_chains_ragged,
  *     sp_ecdsa_verify_batch (per-signature ladder), sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch,
  *     sp_public_key_batch -
  *     run on one of 16 host lanes (own stream, own staging buffer) and hold the lock only while a
@@ -89,7 +90,7 @@ int sp_init(int device, int window_bits);
  *     sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch, sp_public_key_batch take the context of the host lane
  *     they are handed (lanes go round-robin over the contexts, so concurrent host threads spread over the
  *     devices), and one call of sp_pedersen_batch / sp_ecdsa_verify_batch with 16384 items or more is cut into
- *     one contiguous slice per context, the slices running side by side on host threads of the library; sp_pedersen_batch_dev, sp_pedersen_chains_dev, sp_merkle_build_dev, sp_merkle_forest_dev,
+ *     one contiguous slice per context, the slices running side by side on host threads of the library; sp_pedersen_batch_dev, sp_pedersen_chains_dev, sp_pedersen_chains_ragged_dev, sp_merkle_build_dev, sp_merkle_forest_dev,
  *     sp_commit_rows_dev, sp_ecdsa_verify_batch_dev, sp_ecdsa_sign_batch_dev, sp_ecdsa_sign_rfc6979_batch_dev and
  *     sp_public_key_batch_dev run on the device their pointers live on (the stream
  *     must belong to that device);
@@ -140,6 +141,19 @@ int sp_pedersen_chains_dev(const uint64_t* elems, size_t width, size_t depth, ui
                            uint8_t* status, void* stream);
 /* same with host pointers (status: OR of the item status bytes) */
 int sp_pedersen_chains(const uint64_t* elems, size_t width, size_t depth, uint64_t* out, uint8_t* status);
+/* n independent left-fold chains of unequal length, chain-major: chain i = elems[4*off[i] .. 4*off[i+1]),
+ * off = n + 1 HOST offsets in felts, off[0] = 0, non-decreasing by >= 1.  out: n felts.  status: n bytes or NULL.
+ * out[i] = H(...H(H(e0,e1),e2)...,e_{len-1}), the element itself for a chain of one; status[i] = OR of the status
+ * bytes of chain i's hashes (SP_HASH_OUT_OF_RANGE also for the only word of a one-word chain).  The message hashes
+ * of a mixed transaction batch (execute_batch.cairo:296-343: chains of 2 to 6 words) and position leaves of
+ * different asset counts (position/hash.cairo:22-74) in ONE launch that lasts as long as its longest chain; batches
+ * above the largest launch class (8192 chains) go out as consecutive slices on the same stream.  A zero-length
+ * chain or off[0] != 0: SP_ERR_BAD_ARGUMENT, nothing is written.  The _dev call enqueues and returns; it has
+ * copied `off` by then. */
+int sp_pedersen_chains_ragged_dev(const uint64_t* elems, const uint32_t* off, size_t n,
+                                  uint64_t* out, uint8_t* status, void* stream);   /* elems/out/status on the device */
+int sp_pedersen_chains_ragged(const uint64_t* elems, const uint32_t* off, size_t n,
+                              uint64_t* out, uint8_t* status);                     /* all host pointers, runs on a host lane */
 
 /* ---- Merkle trees with node = pedersen_hash(left, right) ------------------------------------- */
 /* (merkle_multi_update call sites services/perpetual/cairo/state/state.cairo:155-173)           */

@@ -15,6 +15,7 @@
 //                                      64 lanes touch 64 consecutive dwords
 // Algorithmic bytes per hash: 96 (two felts in, one out).  The kernel is VALU bound
 // (~1.75e3 VALU instructions per window addition, 39e3 per hash), not HBM bound - see DESIGN.md.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -647,6 +648,99 @@ ped_chain_kernel(const uint64_t* __restrict__ first, const uint64_t* __restrict_
   }
 }
 
+// Hash chains of UNEQUAL length as one launch: the lane groups, the `dup` idiom and the LDS hand-over of
+// ped_chain_kernel, with the chains packed chain-major (CSR): chain e owns the felts off[e] .. off[e + 1) of `elems`
+// and folds them from the left; a chain of one word is that word.  The loop holds barriers, so its bound is the
+// same for the whole block: the largest step count among the block's chains (an LDS maximum) - a block of short
+// chains retires early.  A group whose chain has ended goes on hashing its own first word (a harmless operand: full
+// execution mask for the lane exchanges of quad_hash, and nothing is read behind the chain's last word), arrives at
+// both barriers and writes nothing more: neither its slot, nor `out`, nor status.  status[e] (optional) = OR of the
+// steps' status bytes; of the 2^dup groups that share a chain only the first one writes.
+template <int LOG_Q>
+__global__ void __launch_bounds__(256)
+ped_chain_ragged_kernel(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ off, size_t n,
+                        const aff_packed* __restrict__ ped, int w0, int log2e, int nwin_plan,
+                        unsigned* __restrict__ flag, uint8_t* __restrict__ status, uint64_t* __restrict__ out, int dup) {
+  constexpr int QUADS = 1 << LOG_Q, LANES = 4 * QUADS;
+  __shared__ uint64_t slot[256 / LANES][4];
+  __shared__ int block_steps;
+  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t e_raw = gt / ((size_t)LANES << dup);
+  const int g = (int)(gt % LANES), grp = (int)(threadIdx.x / LANES);
+  const bool active = e_raw < n;
+  const size_t e = active ? e_raw : n - 1;  // clamped groups repeat the last chain: the same length, no write
+  const bool writer = active && g == 0 && ((gt / LANES) & (((size_t)1 << dup) - 1)) == 0;
+  const uint32_t o0 = off[e];
+  const int steps = (int)(off[e + 1] - o0) - 1;  // every group of one chain (dup) reads the same two offsets
+  if (threadIdx.x == 0) block_steps = 0;
+  __syncthreads();
+  if (g == 0 && steps > 0) atomicMax(&block_steps, steps);
+  __syncthreads();
+  const int bound = block_steps;
+  const uint64_t* e0 = elems + 4 * (size_t)o0;
+  uint8_t st = SP_HASH_OK;
+  if (steps == 0 && writer) {  // a chain of one word
+    const u256 v = ld_u256(e0);
+    if (!u256_lt(v, U256_P)) st = SP_HASH_OUT_OF_RANGE;
+    st_u256(out + 4 * e, v);
+    if (status) status[e] = st;
+    if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);
+  }
+  const uint64_t* h = e0;
+  const uint64_t* w = e0 + 4;
+  for (int j = 0; j < bound; ++j, w += 4) {
+    const bool live = j < steps;  // the same on every lane of the group
+    const uint64_t* fx = live ? h : e0;
+    const uint64_t* fy = live ? w : e0;
+    bool unhashable;
+    const u256 xa = quad_hash<LOG_Q, false>(fx, fy, 0, nullptr, 0, 0, ped, w0, log2e, nwin_plan, g, &unhashable);
+    if (live && g == 0) {
+      // every word is a caller's value; the running hash is one only at the first step
+      if (!u256_lt(ld_u256(w), U256_P) || (j == 0 && !u256_lt(ld_u256(h), U256_P))) st |= SP_HASH_OUT_OF_RANGE;
+      else if (unhashable) st |= SP_HASH_UNHASHABLE;
+    }
+    __syncthreads();  // every lane of the block has taken its windows of this step
+    if (live && g == 0) {
+      uint32_t* sl = reinterpret_cast<uint32_t*>(slot[grp]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) sl[k] = xa.w[k];
+      if (j == steps - 1 && writer) {
+        st_u256(out + 4 * e, xa);
+        if (status) status[e] = st;
+        if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);
+      }
+    }
+    __syncthreads();
+    h = slot[grp];
+  }
+}
+
+// The fallback of the ragged chains (no fused kernel for the plan or the switches): the last launch after the
+// per-step launches.  Sorted position k holds chain perm[k]; its running hash is work[k], the status byte of its
+// step j is step_status[step_off[j] + k]; a chain of one word is copied (and range-checked) here.
+__global__ void __launch_bounds__(256)
+ped_chain_ragged_scatter_kernel(const uint64_t* __restrict__ work, const uint64_t* __restrict__ elems,
+                                const uint32_t* __restrict__ off, const uint32_t* __restrict__ perm,
+                                const uint32_t* __restrict__ step_off, const uint8_t* __restrict__ step_status, size_t n,
+                                unsigned* __restrict__ flag, uint8_t* __restrict__ status, uint64_t* __restrict__ out) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const uint32_t c = perm[k];
+  const uint32_t o0 = off[c], len = off[c + 1] - o0;
+  uint8_t st = SP_HASH_OK;
+  u256 v;
+  if (len == 1) {
+    v = ld_u256(elems + 4 * (size_t)o0);
+    if (!u256_lt(v, U256_P)) st = SP_HASH_OUT_OF_RANGE;
+    if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);  // the step launches have reported theirs
+  } else {
+    v = ld_u256(work + 4 * k);
+    for (uint32_t j = 1; j < len; ++j) st |= step_status[(size_t)step_off[j] + k];
+  }
+  st_u256(out + 4 * (size_t)c, v);
+  if (status) status[c] = st;
+}
+
 // The small levels of a DENSE forest (at most 2048 hashes per level: the eight-quad size class) as one launch per
 // FOUR levels: a block of 8 lane groups (256 threads = one wave per SIMD of its CU: two blocks' waves on one SIMD
 // would halve the speed of both chains) takes 2^L consecutive nodes of level j (L <= 4 levels remain inside every
@@ -941,17 +1035,21 @@ struct Scratch {
 static std::map<StreamKey, DeviceBuffer> g_stream_scratch;
 int get_scratch_public(size_t n, Scratch& s, hipStream_t st);
 static int get_scratch(size_t n, Scratch& s, hipStream_t st) { return get_scratch_public(n, s, st); }
-int get_scratch_public(size_t n, Scratch& s, hipStream_t st) {
+// The stream's scratch with `tail_bytes` more behind the flag (*tail, 256-byte aligned): the offsets, permutation
+// and status bytes of the ragged chains live there, in the same buffer and under the same rules.
+static int get_scratch_tail(size_t n, size_t tail_bytes, Scratch& s, char** tail, hipStream_t st) {
   DeviceBuffer& buf = g_stream_scratch[stream_key(st)];
   const size_t plane = ((9 * n * sizeof(int32_t)) + 255) & ~(size_t)255;
-  SP_HIP(buf.reserve(3 * plane + 256));
+  SP_HIP(buf.reserve(3 * plane + 256 + tail_bytes));
   char* b = (char*)buf.ptr;
   s.X = (int32_t*)b;
   s.ZZ = (int32_t*)(b + plane);
   s.Pre = (int32_t*)(b + 2 * plane);
   s.flag = (unsigned*)(b + 3 * plane);
+  if (tail) *tail = b + 3 * plane + 256;
   return SP_OK;
 }
+int get_scratch_public(size_t n, Scratch& s, hipStream_t st) { return get_scratch_tail(n, 0, s, nullptr, st); }
 
 static size_t g_finish_lanes = getenv("STARKPERP_FINISH_LANES") ? (size_t)atoll(getenv("STARKPERP_FINISH_LANES")) : 65536;
 // Lanes one round of the chip holds (a development knob).  The level plan cuts a level into n_bulk = a multiple of
@@ -996,9 +1094,11 @@ static size_t finish_threads(size_t n) {
   return ((n + K - 1) / K + 3) & ~(size_t)3;  // whole DPP quads: a quad shares one inversion
 }
 
+void release_ragged_stage();
 void release_pedersen_state() {
   for (auto& kv : g_stream_scratch) kv.second.release();
   g_stream_scratch.clear();
+  release_ragged_stage();
   for (hipEvent_t e : g_prof.ev) (void)hipEventDestroy(e);
   g_prof.ev.clear();
   g_prof.units.clear();
@@ -1258,6 +1358,152 @@ static int enqueue_pedersen_impl(const uint64_t* x, size_t xs, const uint64_t* y
   return SP_OK;
 }
 
+// ---- chains of unequal length (sp_pedersen_chains_ragged[_dev]) ----------------------------------
+static bool g_chain_ragged = getenv("STARKPERP_NO_CHAIN_RAGGED") == nullptr;  // A/B switch
+// Host-side staging of a ragged call's offsets (and, in the fallback, its permutation and index pairs): page-locked,
+// one per stream, so that the caller's array is consumed before the call returns and the copy to the device is a
+// true asynchronous DMA.  The event marks the last copy out of the buffer: it is waited for before the buffer is
+// written again - the only wait of a ragged _dev call, and one for a copy that has long run when the next call comes.
+struct RaggedStage {
+  PinnedBuffer host;
+  hipEvent_t copied = nullptr;
+  bool pending = false;
+};
+static std::map<StreamKey, RaggedStage> g_ragged_stage;
+void release_ragged_stage() {
+  for (auto& kv : g_ragged_stage) {
+    if (kv.second.copied) (void)hipEventDestroy(kv.second.copied);
+    kv.second.host.release();
+  }
+  g_ragged_stage.clear();
+}
+// `bytes` of metadata at `meta` (host) -> d_meta, through the stream's page-locked buffer.
+static int ragged_stage_copy(const void* meta, size_t bytes, void* d_meta, hipStream_t st) {
+  RaggedStage& rs = g_ragged_stage[stream_key(st)];
+  if (rs.pending) {
+    SP_HIP(hipEventSynchronize(rs.copied));
+    rs.pending = false;
+  }
+  if (rs.copied == nullptr) SP_HIP(hipEventCreateWithFlags(&rs.copied, hipEventDisableTiming));
+  SP_HIP(rs.host.reserve(bytes));
+  std::memcpy(rs.host.ptr, meta, bytes);
+  SP_HIP(hipMemcpyAsync(d_meta, rs.host.ptr, bytes, hipMemcpyHostToDevice, st));
+  SP_HIP(hipEventRecord(rs.copied, st));
+  rs.pending = true;
+  return SP_OK;
+}
+// Largest batch one ragged launch takes under the current window plan and switches: the top of the size classes
+// of enqueue_pedersen_chain (0: no fused kernel - the per-step fallback serves the call).
+static size_t chain_ragged_cap() {
+  const int nwin = ctx().plan.nwin;
+  if (!g_chain_ragged || !g_quad_enabled || nwin > 64) return 0;
+  if (nwin >= 4 && g_quad2_enabled) return 4 * g_quad_max;
+  if (nwin >= 8) return 2 * g_quad_max;
+  if (nwin >= 16) return g_quad_max;
+  return 0;
+}
+// n chains, chain i = felts off[i] .. off[i + 1) of `elems` (device), `off` = n + 1 validated HOST offsets; out and
+// status (n bytes or null) on the device.  Enqueues on `st` and returns; the caller holds the context lock.
+// Fused: consecutive slices of at most chain_ragged_cap() chains, one ped_chain_ragged_kernel launch each.
+// Fallback: the chains sorted by falling length (a permutation), so that the chains still running at step j are a
+// prefix; step j is one enqueue_pedersen launch over that prefix in gathered mode - the running hashes and a copy
+// of the words share one work buffer, the index pairs address it - and a last launch puts hashes and status bytes
+// back in the caller's order.
+int enqueue_pedersen_chain_ragged(const uint64_t* elems, const uint32_t* off, size_t n, uint64_t* out, uint8_t* status,
+                                  hipStream_t st) {
+  if (n == 0) return SP_OK;
+  Context& c = ctx();
+  const int w0 = c.plan.bits[0], log2e = c.plan.log2e, nwin = c.plan.nwin;
+  const size_t total = off[n];
+  const size_t cap = chain_ragged_cap();
+  Scratch s;
+  char* tail = nullptr;
+  if (cap != 0) {
+    int rc = get_scratch_tail(1, (n + 1) * sizeof(uint32_t), s, &tail, st);
+    if (rc != SP_OK) return rc;
+    SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
+    uint32_t* d_off = (uint32_t*)tail;
+    rc = ragged_stage_copy(off, (n + 1) * sizeof(uint32_t), d_off, st);
+    if (rc != SP_OK) return rc;
+    for (size_t b = 0; b < n; b += cap) {
+      const size_t m = n - b < cap ? n - b : cap;
+      int log_q = 1;  // the size classes of enqueue_pedersen_chain; m <= cap always has one
+      if (m <= g_quad_max && nwin >= 16) log_q = 3;
+      else if (m <= 2 * g_quad_max && nwin >= 8) log_q = 2;
+      int dup = 0;
+      while ((4 << (log_q + dup)) < 64 && ((m * 4) << (log_q + dup + 1)) <= 65536) ++dup;  // up to one chain per wave
+      if (g_quad_no_dup) dup = 0;
+      const unsigned blocks = (unsigned)((((m * 4) << (log_q + dup)) + 255) / 256);
+#define SP_LAUNCH_RAGGED(LOGQ)                                                                                       \
+  hipLaunchKernelGGL((ped_chain_ragged_kernel<LOGQ>), dim3(blocks), dim3(256), 0, st, elems, d_off + b, m, c.ped, w0, \
+                     log2e, nwin, s.flag, status ? status + b : nullptr, out + 4 * b, dup)
+      if (log_q == 3) SP_LAUNCH_RAGGED(3);
+      else if (log_q == 2) SP_LAUNCH_RAGGED(2);
+      else SP_LAUNCH_RAGGED(1);
+#undef SP_LAUNCH_RAGGED
+      SP_HIP(hipGetLastError());
+    }
+    return SP_OK;
+  }
+  // ---- fallback ----
+  if (n + total > 0x7fffffffull) { set_error("ragged chains: more than 2^31 felts"); return SP_ERR_BAD_ARGUMENT; }
+  std::vector<uint32_t> perm(n);
+  for (size_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
+  std::stable_sort(perm.begin(), perm.end(),
+                   [&](uint32_t a, uint32_t b) { return off[a + 1] - off[a] > off[b + 1] - off[b]; });
+  const size_t maxlen = off[perm[0] + 1] - off[perm[0]];
+  const size_t n_pairs = total - n;  // sum over the steps of the chains still running = all hashes of the call
+  // metadata, one copy: off[n + 1] | perm[n] | step_off[maxlen] | index pairs (2 x n_pairs)
+  std::vector<uint32_t> meta(n + 1 + n + maxlen + 2 * n_pairs);
+  std::memcpy(meta.data(), off, (n + 1) * sizeof(uint32_t));
+  std::memcpy(meta.data() + n + 1, perm.data(), n * sizeof(uint32_t));
+  uint32_t* step_off = meta.data() + 2 * n + 1;
+  uint32_t* pairs = step_off + maxlen;
+  std::vector<size_t> running(maxlen, 0);  // running[j] = chains longer than j words
+  size_t m = n, pos = 0;
+  for (size_t j = 1; j < maxlen; ++j) {
+    while (m > 0 && off[perm[m - 1] + 1] - off[perm[m - 1]] <= j) --m;
+    running[j] = m;
+    step_off[j] = (uint32_t)pos;
+    for (size_t k = 0; k < m; ++k) {
+      const uint32_t o = (uint32_t)n + off[perm[k]];
+      pairs[2 * (pos + k)] = j == 1 ? o : (uint32_t)k;  // left: the chain's first word, later its running hash
+      pairs[2 * (pos + k) + 1] = o + (uint32_t)j;       // right: word j of the chain
+    }
+    pos += m;
+  }
+  if (maxlen > 0) step_off[0] = 0;
+  const size_t meta_bytes = (meta.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
+  const size_t stat_bytes = (n_pairs + 255) & ~(size_t)255;
+  int rc = get_scratch_tail(n, meta_bytes + stat_bytes + (n + total) * 32, s, &tail, st);
+  if (rc != SP_OK) return rc;
+  SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
+  uint32_t* d_meta = (uint32_t*)tail;
+  uint8_t* d_stat = (uint8_t*)(tail + meta_bytes);
+  uint64_t* d_work = (uint64_t*)(tail + meta_bytes + stat_bytes);
+  rc = ragged_stage_copy(meta.data(), meta.size() * sizeof(uint32_t), d_meta, st);
+  if (rc != SP_OK) return rc;
+  SP_HIP(hipMemcpyAsync(d_work + 4 * n, elems, total * 32, hipMemcpyDeviceToDevice, st));
+  const int2* d_pairs = reinterpret_cast<const int2*>(d_meta + 2 * n + 1 + maxlen);
+  for (size_t j = 1; j < maxlen; ++j) {
+    rc = enqueue_pedersen(d_work, 1, d_work, 1, d_work, 1, d_stat + step_off[j], s.flag, running[j], st, s,
+                          d_pairs + step_off[j]);
+    if (rc != SP_OK) return rc;
+  }
+  hipLaunchKernelGGL(ped_chain_ragged_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_work, elems,
+                     d_meta, d_meta + n + 1, d_meta + 2 * n + 1, d_stat, n, s.flag, status, out);
+  SP_HIP(hipGetLastError());
+  return SP_OK;
+}
+// off[0] = 0 and every chain holds at least one word; the text goes to sp_last_error.
+static bool ragged_offsets_ok(const uint32_t* off, size_t n) {
+  if (off == nullptr || off[0] != 0) { set_error("ragged chains: off[0] must be 0"); return false; }
+  for (size_t i = 0; i < n; ++i) {
+    if (off[i + 1] <= off[i]) { set_error("ragged chains: every chain needs at least one element"); return false; }
+  }
+  return true;
+}
+
 }  // namespace sp
 
 using namespace sp;
@@ -1428,6 +1674,53 @@ int sp_pedersen_chains(const uint64_t* elems, size_t width, size_t depth, uint64
   SP_HIP(hipStreamSynchronize(L.stream));
   if (stage) std::memcpy(out, stage + in_bytes, out_bytes);
   if (status) *status = st8;
+  return SP_OK;
+}
+
+// Chains of unequal length in one call (ped_chain_ragged_kernel): chain i = the felts off[i] .. off[i + 1) of
+// elems.  Enqueues and returns; the HOST array `off` has been copied when it does.
+int sp_pedersen_chains_ragged_dev(const uint64_t* elems, const uint32_t* off, size_t n, uint64_t* out, uint8_t* status,
+                                  void* stream) {
+  CtxByPointer sp_ctx_sel__(elems);  // the context of the device these pointers live on
+  SP_REQUIRE_READY();
+  if (n == 0) return SP_OK;
+  if (!ragged_offsets_ok(off, n)) return SP_ERR_BAD_ARGUMENT;
+  ctx_lock lk(ctx().mu);
+  return enqueue_pedersen_chain_ragged(elems, off, n, out, status, (hipStream_t)stream);
+}
+
+// Host-pointer variant: one staged round trip on a host lane (see sp_pedersen_chains), status = n bytes or NULL.
+int sp_pedersen_chains_ragged(const uint64_t* elems, const uint32_t* off, size_t n, uint64_t* out, uint8_t* status) {
+  LaneScope ls(0);  // the primary context, as sp_pedersen_chains
+  SP_REQUIRE_READY();
+  if (n == 0) return SP_OK;
+  if (!ragged_offsets_ok(off, n)) return SP_ERR_BAD_ARGUMENT;
+  if (ls.open() != SP_OK) return SP_ERR_HIP;
+  HostLane& L = *ls.lane;
+  const size_t total = off[n];
+  const size_t in_bytes = total * 32, out_bytes = n * 32 + n;  // the status bytes travel behind the hashes
+  SP_HIP(L.io.reserve(in_bytes + out_bytes + 64));
+  uint64_t* d_el = (uint64_t*)L.io.ptr;
+  uint64_t* d_out = d_el + 4 * total;
+  uint8_t* d_st = (uint8_t*)(d_out + 4 * n);
+  char* stage = nullptr;
+  if (in_bytes + out_bytes <= PINNED_STAGE_MAX && L.hio.reserve(in_bytes + out_bytes) == hipSuccess) stage = (char*)L.hio.ptr;
+  else (void)hipGetLastError();
+  if (stage) std::memcpy(stage, elems, in_bytes);
+  SP_HIP(hipMemcpyAsync(d_el, stage ? (const void*)stage : (const void*)elems, in_bytes, hipMemcpyHostToDevice, L.stream));
+  int rc = sp_pedersen_chains_ragged_dev(d_el, off, n, d_out, d_st, L.stream);
+  if (rc != SP_OK) return rc;
+  if (stage) {
+    SP_HIP(hipMemcpyAsync(stage + in_bytes, d_out, out_bytes, hipMemcpyDeviceToHost, L.stream));
+  } else {
+    SP_HIP(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, L.stream));
+    if (status) SP_HIP(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, L.stream));
+  }
+  SP_HIP(hipStreamSynchronize(L.stream));
+  if (stage) {
+    std::memcpy(out, stage + in_bytes, n * 32);
+    if (status) std::memcpy(status, stage + in_bytes + n * 32, n);
+  }
   return SP_OK;
 }
 

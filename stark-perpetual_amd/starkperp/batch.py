@@ -88,6 +88,30 @@ def pedersen_chains_many(chains):
     return unpack_felts(out, width)
 
 
+def pedersen_chains_ragged(chains):
+    """Chains of any lengths >= 1 in ONE library call (sp_pedersen_chains_ragged: one launch that lasts as long
+    as the longest chain): [H(...H(H(c[0], c[1]), c[2])..., c[-1]) for c in chains], a chain of one word being
+    that word.  The words go out chain after chain (CSR: chain i = words off[i] .. off[i + 1])."""
+    n = len(chains)
+    if n == 0:
+        return []
+    flat, off = [], [0]
+    for c in chains:
+        assert len(c) >= 1
+        assert min(c) >= 0 and max(c) < FIELD_PRIME
+        flat.extend(c)
+        off.append(len(flat))
+    assert off[-1] < 2**32
+    lib = _lib.ensure_init()
+    out, st = new_felts(n), new_bytes(n)
+    _lib.check(lib.sp_pedersen_chains_ragged(pack_felts(flat), (ctypes.c_uint32 * (n + 1))(*off), n, out, st),
+               "sp_pedersen_chains_ragged")
+    for code in bytes(st)[:n]:
+        if code:
+            _raise_hash_status(2 if code & 2 else 1)
+    return unpack_felts(out, n)
+
+
 def pedersen_points_many(xs, ys):
     """[pedersen_hash_as_point(x, y) ...] (signature.py:300-318) - the full affine point."""
     n = len(xs)

@@ -79,6 +79,27 @@ def pedersen_chains(words) -> np.ndarray:
     return out
 
 
+def pedersen_chains_ragged(words, offsets):
+    """Chains of unequal length in one call (sp_pedersen_chains_ragged): words uint64[total, 4] chain after chain,
+    offsets uint32[n + 1] (offsets[0] = 0, rising by at least 1, offsets[n] = total); chain i folds the rows
+    offsets[i] .. offsets[i + 1) from the left, a chain of one row being that row.
+    Returns (hashes uint64[n, 4], status uint8[n]).  Unlike its neighbours this call does NOT raise for a word
+    outside [0, p) or an unhashable step: status[i] carries HASH_OUT_OF_RANGE / HASH_UNHASHABLE bits for chain i
+    alone and the other rows are good - a mixed transaction batch wants to know WHICH item was bad."""
+    w = _felts(words)
+    off = np.ascontiguousarray(offsets, dtype=np.uint32)
+    assert off.ndim == 1 and off.shape[0] >= 1, "offsets are uint32[n + 1]"
+    n = off.shape[0] - 1
+    assert int(off[-1]) == w.shape[0], "offsets[n] must be the number of rows"
+    out = np.empty((n, 4), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    if n == 0:
+        return out, st
+    _lib.check(_lib.ensure_init().sp_pedersen_chains_ragged(_ptr(w), _ptr(off), n, _ptr(out), _ptr(st)),
+               "sp_pedersen_chains_ragged")
+    return out, st
+
+
 def verify_codes(z, r, s, qx, qy=None, key_tables=None) -> np.ndarray:
     """Result codes (include/starkperp.h SP_VERIFY_*) of verify(z, r, s, key) per row; qy None = x-only
     keys (signature.py:229-238).  key_tables as in starkperp.batch.verify_codes."""

@@ -228,6 +228,36 @@ def get_price_msg(oracle_name: int, asset_pair: int, timestamp: int, price: int,
 
 
 # ---- batch additions --------------------------------------------------------------------------
+# The hash-chain words of one message, from the argument tuple its scalar builder takes.
+def _transfer_chain(t):
+    (asset_id, asset_id_fee, receiver_public_key, sender, receiver, fee_pos, nonce, amount, max_fee, expiration) = t
+    w0, w1 = _transfer_words(TRANSFER, sender, receiver, fee_pos, nonce, amount, max_fee, expiration)
+    return [asset_id, asset_id_fee, receiver_public_key, w0, w1]
+
+
+def _conditional_transfer_chain(t):
+    (asset_id, asset_id_fee, receiver_public_key, condition, sender, receiver, fee_pos, nonce, amount, max_fee,
+     expiration) = t
+    w0, w1 = _transfer_words(CONDITIONAL_TRANSFER, sender, receiver, fee_pos, nonce, amount, max_fee, expiration)
+    return [asset_id, asset_id_fee, receiver_public_key, condition, w0, w1]
+
+
+def _withdrawal_to_address_chain(w):
+    asset_id_collateral, position_id, eth_address, nonce, expiration, amount = w
+    address = int(eth_address, 16) if isinstance(eth_address, str) else int(eth_address)
+    return [asset_id_collateral, address, _withdrawal_word(position_id, nonce, amount, expiration)]
+
+
+def _withdrawal_chain(w):
+    asset_id_collateral, position_id, nonce, expiration, amount = w
+    return [asset_id_collateral, _withdrawal_word(position_id, nonce, amount, expiration, WITHDRAWAL)]
+
+
+def _price_chain(p):
+    oracle_name, asset_pair, timestamp, price = p
+    return [(asset_pair << 40) + oracle_name, (price << 32) + timestamp]
+
+
 def limit_order_msgs_many(orders: Sequence[Sequence[int]]):
     """Message hashes of many limit orders (each a 10-tuple in get_limit_order_msg argument
     order): four GPU launches of width len(orders) instead of 4 * len(orders) scalar hashes."""
@@ -237,23 +267,12 @@ def limit_order_msgs_many(orders: Sequence[Sequence[int]]):
 
 def transfer_msgs_many(transfers: Sequence[Sequence[int]]):
     """Many transfers (10-tuples in get_transfer_msg argument order): depth-5 chains."""
-    words = []
-    for (asset_id, asset_id_fee, receiver_public_key, sender, receiver, fee_pos, nonce, amount,
-         max_fee, expiration) in transfers:
-        w0, w1 = _transfer_words(TRANSFER, sender, receiver, fee_pos, nonce, amount, max_fee, expiration)
-        words.append([asset_id, asset_id_fee, receiver_public_key, w0, w1])
-    return batch.pedersen_chains_many(words)
+    return batch.pedersen_chains_many([_transfer_chain(t) for t in transfers])
 
 
 def conditional_transfer_msgs_many(transfers: Sequence[Sequence[int]]):
     """Many conditional transfers (11-tuples in get_conditional_transfer_msg order): depth 6."""
-    words = []
-    for (asset_id, asset_id_fee, receiver_public_key, condition, sender, receiver, fee_pos, nonce,
-         amount, max_fee, expiration) in transfers:
-        w0, w1 = _transfer_words(CONDITIONAL_TRANSFER, sender, receiver, fee_pos, nonce, amount, max_fee,
-                                 expiration)
-        words.append([asset_id, asset_id_fee, receiver_public_key, condition, w0, w1])
-    return batch.pedersen_chains_many(words)
+    return batch.pedersen_chains_many([_conditional_transfer_chain(t) for t in transfers])
 
 
 def price_msgs_many(prices: Sequence[Sequence[int]]):
@@ -267,11 +286,7 @@ def price_msgs_many(prices: Sequence[Sequence[int]]):
 def withdrawal_to_address_msgs_many(withdrawals: Sequence[Sequence]):
     """Many withdrawals to an address (6-tuples in get_withdrawal_to_address_msg argument order,
     eth_address a hex string or an int): depth-3 chains."""
-    words = []
-    for asset_id_collateral, position_id, eth_address, nonce, expiration, amount in withdrawals:
-        address = int(eth_address, 16) if isinstance(eth_address, str) else int(eth_address)
-        words.append([asset_id_collateral, address, _withdrawal_word(position_id, nonce, amount, expiration)])
-    return batch.pedersen_chains_many(words)
+    return batch.pedersen_chains_many([_withdrawal_to_address_chain(w) for w in withdrawals])
 
 
 def withdrawal_msgs_many(withdrawals: Sequence[Sequence[int]]):
@@ -284,24 +299,44 @@ def withdrawal_msgs_many(withdrawals: Sequence[Sequence[int]]):
 
 def withdrawal_hashes_many(withdrawals: Sequence[Sequence[int]]):
     """withdrawal_hash for a mixed batch (7-tuples: asset_id_collateral, position_id, owner_key,
-    public_key, nonce, expiration_timestamp, amount): the type-6 messages as one batch of single hashes,
-    the type-7 ones as depth-3 chains; results in input order."""
-    old = [i for i, w in enumerate(withdrawals) if w[2] == w[3]]
-    new = [i for i, w in enumerate(withdrawals) if w[2] != w[3]]
-    out = [None] * len(withdrawals)
-    if old:
-        got = withdrawal_msgs_many([(withdrawals[i][0], withdrawals[i][1], withdrawals[i][4],
-                                     withdrawals[i][5], withdrawals[i][6]) for i in old])
-        for i, v in zip(old, got):
-            out[i] = v
-    if new:
-        got = batch.pedersen_chains_many([
-            [withdrawals[i][0], withdrawals[i][2],
-             _withdrawal_word(withdrawals[i][1], withdrawals[i][4], withdrawals[i][6], withdrawals[i][5])]
-            for i in new])
-        for i, v in zip(new, got):
-            out[i] = v
-    return out
+    public_key, nonce, expiration_timestamp, amount), results in input order.  A batch of one kind keeps its
+    equal-depth call (type 6: single hashes, type 7: depth-3 chains); a batch that holds both goes out as ONE
+    ragged call of 2- and 3-word chains (batch.pedersen_chains_ragged)."""
+    old = [w[2] == w[3] for w in withdrawals]
+    if all(old):
+        return withdrawal_msgs_many([(w[0], w[1], w[4], w[5], w[6]) for w in withdrawals])
+    words = [[w[0], _withdrawal_word(w[1], w[4], w[6], w[5], WITHDRAWAL)] if is_old else
+             [w[0], w[2], _withdrawal_word(w[1], w[4], w[6], w[5])] for w, is_old in zip(withdrawals, old)]
+    if not any(old):
+        return batch.pedersen_chains_many(words)
+    return batch.pedersen_chains_ragged(words)
+
+
+MIXED_KINDS = {  # message_hashes_mixed: kind -> the words of one message from the tuple its *_many function takes
+    "limit_order": lambda a: _limit_order_words(*a),
+    "transfer": _transfer_chain,
+    "conditional_transfer": _conditional_transfer_chain,
+    "withdrawal": _withdrawal_chain,
+    "withdrawal_to_address": _withdrawal_to_address_chain,
+    "price": _price_chain,
+}
+
+
+def message_hashes_mixed(items: Sequence, hash_function: Callable[..., int] = None):
+    """The message hashes of a batch that interleaves transaction types (execute_batch.cairo:296-343): items =
+    (kind, args) with kind one of MIXED_KINDS and args the tuple the matching *_many function takes.  Returns the
+    hashes in input order from ONE library call: the chains (2 words for prices and old-API withdrawals, 3 for
+    withdrawals to an address, 5 for limit orders and transfers, 6 for conditional transfers) run in one launch
+    that lasts as long as the longest of them.  With `hash_function=` the same words are folded on the host with
+    that function (the reference's injection seam)."""
+    words = []
+    for kind, args in items:
+        if kind not in MIXED_KINDS:
+            raise ValueError("unknown message kind %r" % (kind,))
+        words.append(MIXED_KINDS[kind](args))
+    if hash_function is not None:
+        return [_fold(hash_function, w) for w in words]
+    return batch.pedersen_chains_ragged(words)
 
 
 def verify_price_signatures_many(prices: Sequence[Sequence[int]], signatures: Sequence[Sequence[int]],

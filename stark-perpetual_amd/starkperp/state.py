@@ -40,18 +40,13 @@ def position_hash(position: Position) -> int:
 
 
 def position_hashes_many(positions: Iterable[Position]) -> List[int]:
-    """Many position leaves: chains are grouped by depth (n_assets + 3 words) and each group runs
-    as batched launches."""
+    """Many position leaves (chains of n_assets + 3 words).  Positions of one asset count run as equal-depth
+    chains (batch.pedersen_chains_many); a batch whose asset counts differ goes out as ONE ragged call
+    (batch.pedersen_chains_ragged) that lasts as long as its longest chain, not one call per depth."""
     words = [position_words(p) for p in positions]
-    out = [0] * len(words)
-    by_depth: Dict[int, List[int]] = {}
-    for i, w in enumerate(words):
-        by_depth.setdefault(len(w), []).append(i)
-    for depth, idxs in by_depth.items():
-        res = batch.pedersen_chains_many([words[i] for i in idxs])
-        for i, r in zip(idxs, res):
-            out[i] = r
-    return out
+    if len({len(w) for w in words}) <= 1:
+        return batch.pedersen_chains_many(words)
+    return batch.pedersen_chains_ragged(words)
 
 
 def order_id_of(message_hash: int) -> int:
@@ -225,9 +220,10 @@ class LibrarySparseTree:
 def hash_position_updates(updates: Sequence[Tuple[int, Position, Position]]):
     """position/hash.cairo:76-131: (key, prev_position, new_position) -> (key, prev_hash, new_hash);
     an unchanged position is hashed once."""
-    prev = position_hashes_many([u[1] for u in updates])
     changed = [i for i, u in enumerate(updates) if u[1] != u[2]]
-    new_h = position_hashes_many([updates[i][2] for i in changed])
+    # previous and new leaves of all updates as one batch: one call, ragged when the asset counts differ
+    both = position_hashes_many([u[1] for u in updates] + [updates[i][2] for i in changed])
+    prev, new_h = both[: len(updates)], both[len(updates):]
     out = [(u[0], p, p) for u, p in zip(updates, prev)]
     for i, hnew in zip(changed, new_h):
         out[i] = (updates[i][0], prev[i], hnew)
