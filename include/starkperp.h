@@ -52,9 +52,12 @@ extern "C" {
 #define SP_ERR_TABLE_BUILD (-4)
 #define SP_ERR_CACHE_FULL (-5) /* sp_ecdsa_register_keys: no free key-table slot */
 
-/* per-item status of sp_pedersen_* (signature.py:300-318) */
+/* per-item status of sp_pedersen_* (signature.py:300-318).  sp_pedersen_batch[_dev] write status[i] for every
+ * item, exactly: SP_HASH_OUT_OF_RANGE for item i if and only if x[i] or y[i] is not in [0, p), whatever n is and
+ * wherever in the batch the item sits; the items around it are hashed as usual.  out[i] of an item whose status is
+ * not SP_HASH_OK is unspecified (the kernels differ in what they leave there): read status[i] before out[i]. */
 #define SP_HASH_OK 0
-#define SP_HASH_OUT_OF_RANGE 1 /* an input was not in [0, p): signature.py:307 assertion */
+#define SP_HASH_OUT_OF_RANGE 1 /* an input was not in [0, p): signature.py:307 assertion; out[i] is unspecified */
 #define SP_HASH_UNHASHABLE 2   /* exceptional point collision: signature.py:313 ("Unhashable input.") */
 #define SP_TREE_NOT_COMMITTED 0x80 /* sp_order_batch: a signature did not verify - the tree was left as it was */
 

@@ -59,7 +59,12 @@ def test_edges_and_kats(batch):
 
 def test_out_of_range_raises(batch):
     with pytest.raises(AssertionError):
-        batch.pedersen_hash_many([P], [0])
+        batch.pedersen_hash_many([P], [0])  # asserted in Python: the library is not called
+    # the NumPy entry point hands the operands over as they are: here the DEVICE flags x = p (one hash; every
+    # other launch plan: tests/test_gpu_pedersen_plans.py)
+    from starkperp import batch_np
+    with pytest.raises(AssertionError):
+        batch_np.pedersen_hash_many(batch_np.felts_from_ints([P]), batch_np.felts_from_ints([0]))
 
 
 def test_chain(batch):
@@ -184,8 +189,9 @@ print(hashlib.sha256(repr(out).encode()).hexdigest())
 
 
 def test_bulk_and_split_paths_vs_c_oracle(batch):
-    """Every accumulate variant (1, 2, 4, 8 lanes per hash are picked by batch size) against the C
-    oracle on seeded inputs, plus out-of-range status propagation inside a large batch."""
+    """Accumulate variants picked by batch size (mixed bulk + 8 lanes, 1, 2 lanes per hash, four quads) against the
+    plain C oracle on seeded random inputs, results only.  Per-item status inside a batch and every other size
+    class: tests/test_gpu_pedersen_plans.py."""
     from oracle import cref
     rng = random.Random(77)
     for n in (70000, 40000, 20000, 3000):
