@@ -211,6 +211,44 @@ int sp_tree_root(int tree, uint64_t* root);
 int sp_order_batch(const uint64_t* words, size_t depth, size_t n, const uint64_t* r, const uint64_t* s,
                    const uint64_t* qx, const uint64_t* qy, int tree, const uint64_t* leaves, unsigned id_shift,
                    uint64_t* z_out, uint8_t* verdicts, uint64_t* old_root, uint64_t* new_root, uint8_t* tree_status);
+/* The whole state update of a batch in one call: shared_state_apply_state_updates (services/perpetual/cairo/state/
+ * state.cairo:135-186) - previous and new leaf of every touched position (position/hash.cairo:76-131), merkle_multi_update
+ * of the positions tree (:155-161) and of the orders tree (:167-173) - all or nothing across BOTH trees.
+ *   pos_keys, ord_keys   strictly increasing, below 2^height of their tree, squashed by the caller (state.cairo:67-96)
+ *   prev_words/prev_off  previous leaf of position i = the left-fold chain over prev_words[4 prev_off[i] .. 4 prev_off[i+1])
+ *                        (the convention of sp_pedersen_chains_ragged: n_pos + 1 offsets in felts, prev_off[0] = 0, every
+ *                        chain at least one word)
+ *   new_words/new_off    the new leaf likewise; a chain of length zero (new_off[i+1] == new_off[i]) says that the position
+ *                        is unchanged: it is hashed once and its new leaf is its previous leaf
+ *   ord_prev, ord_new    n_ord felts each: the orders-tree leaves before and after
+ * Every previous leaf is compared ON THE DEVICE with what its tree holds at that key (the empty leaf for a key the tree
+ * has never seen), every new node of both trees is hashed - the positions tree on its stream, the orders tree on its
+ * own, side by side - and both tables are written only if everything checked out.  Otherwise neither is written, both
+ * *_new_root equal their *_old_root and the call still returns SP_OK.
+ *   *batch_status   0: committed; otherwise SP_TREE_NOT_COMMITTED OR-ed with every item status byte and with the
+ *                   SP_HASH_* flags of the two trees' level hashing
+ *   pos_status[i]   (n_pos bytes or NULL) OR of the SP_HASH_* bytes of item i's two chains; SP_STATE_PREV_MISMATCH is
+ *                   added if, and only if, the previous chain's own status is 0 and its hash is not the tree's leaf
+ *   ord_status[i]   (n_ord bytes or NULL) SP_HASH_OUT_OF_RANGE if ord_new[i] >= p; SP_STATE_PREV_MISMATCH if ord_prev[i]
+ *                   is not the tree's leaf (a value >= p never is)
+ * SP_ERR_BAD_ARGUMENT, with no output written: keys not strictly increasing or out of range for the tree's height;
+ * off[0] != 0, a decreasing offset or a previous chain of length zero; an unknown handle; the same handle twice; two
+ * trees on different contexts of sp_init_devices (not supported: both trees of one state live on one device).
+ * n_pos == 0 and / or n_ord == 0 are legal: a tree with nothing to write reports old == new and still takes part in
+ * the all-or-nothing decision.
+ * No hash crosses PCIe: the call uploads the words, one ragged launch sequence hashes previous and new chains into the
+ * positions tree's work buffer, a leaf kernel per tree looks the current leaves up, compares, writes the status bytes
+ * and places the new leaves where the update's level 0 is read from.  Host side: the call holds both trees' mutexes
+ * from start to end (always taken in ascending handle order, so callers that name the same two trees in opposite
+ * roles cannot block each other) and the library lock only while it enqueues; it takes no host lane and starts no
+ * thread.  STARKPERP_TIMELINE=1 prints its host-side marks like sp_order_batch's.  Timing: tools/quick_state_batch.py. */
+#define SP_STATE_PREV_MISMATCH 0x10 /* per item: the previous value given is not what the tree holds */
+int sp_state_batch(int positions_tree, int orders_tree, const uint64_t* pos_keys, size_t n_pos,
+                   const uint64_t* prev_words, const uint32_t* prev_off, const uint64_t* new_words,
+                   const uint32_t* new_off, const uint64_t* ord_keys, const uint64_t* ord_prev,
+                   const uint64_t* ord_new, size_t n_ord, uint64_t* pos_old_root, uint64_t* pos_new_root,
+                   uint64_t* ord_old_root, uint64_t* ord_new_root, uint8_t* pos_status, uint8_t* ord_status,
+                   uint8_t* batch_status);
 int sp_tree_destroy(int tree);
 
 /* ---- Stark-curve ECDSA ------------------------------------------------------------------------ */

@@ -42,6 +42,8 @@ struct PathLevels {  // pedersen.hip ped_path_kernel
 };
 int enqueue_pedersen_path(uint64_t* felts, const uint64_t* emp, unsigned* flag, size_t n, hipStream_t st,
                           const int2* src_all, const PathLevels& pl, const aff_packed* cpts_tree, bool* done);
+int enqueue_pedersen_chain_ragged(const uint64_t* elems, const uint32_t* off, size_t n, uint64_t* out, uint8_t* status,
+                                  hipStream_t st);
 
 static DeviceBuffer g_sparse_buf;
 // empty-subtree roots are a pure function of the empty leaf: cached on the host per leaf value
@@ -380,6 +382,65 @@ tree_get_kernel(const TreeSlot* __restrict__ tab, uint64_t mask, const uint64_t*
 #pragma unroll
   for (int w = 0; w < 4; ++w) out[4 * (size_t)j + w] = v[w];
 }
+// ---- the leaf kernels of sp_state_batch: one thread per item, in front of the update's structure kernels ----
+// Status bits raised by any lane go into the stream's status flag with one atomic per wave.
+__device__ __forceinline__ void tree_raise(unsigned* __restrict__ flag, unsigned bits) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bits |= (unsigned)__shfl_xor((int)bits, o);
+  if ((threadIdx.x & 63) == 0 && bits) atomicOr(flag, bits);
+}
+__device__ __forceinline__ bool tree_leaf_is(const TreeSlot* __restrict__ tab, uint64_t mask, uint64_t key,
+                                             const uint64_t* __restrict__ empty_leaf, const uint64_t* value) {
+  const uint64_t* v = tree_find(tab, mask, 0, key);
+  if (!v) v = empty_leaf;
+  bool same = true;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) same &= v[w] == value[w];
+  return same;
+}
+constexpr uint32_t STATE_UNCHANGED = 0xffffffffu;
+// Positions (position/hash.cairo:76-131): hashes = the n previous leaves, then the leaves of the changed positions;
+// chain_status likewise; map[j] = number of item j among the changed ones, or STATE_UNCHANGED.  Item j: the tree's
+// current leaf at keys[j] against its previous hash (only a previous chain that hashed can mismatch), status[j], and
+// level-0 slot j of the update = changed ? new hash : previous hash.
+__global__ void __launch_bounds__(256)
+state_pos_leaf_kernel(const TreeSlot* __restrict__ tab, uint64_t mask, const uint64_t* __restrict__ keys, unsigned cnt,
+                      const uint64_t* __restrict__ empty_leaf, const uint64_t* __restrict__ hashes,
+                      const uint8_t* __restrict__ chain_status, const uint32_t* __restrict__ map,
+                      uint64_t* __restrict__ level0, uint8_t* __restrict__ status, unsigned* __restrict__ flag) {
+  const unsigned j = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned st = 0;
+  if (j < cnt) {
+    const uint64_t* leaf = hashes + 4 * (size_t)j;
+    st = chain_status[j];
+    if (st == 0 && !tree_leaf_is(tab, mask, keys[j], empty_leaf, leaf)) st = SP_STATE_PREV_MISMATCH;
+    const uint32_t m = map[j];
+    if (m != STATE_UNCHANGED) {
+      st |= chain_status[(size_t)cnt + m];
+      leaf = hashes + 4 * ((size_t)cnt + m);
+    }
+#pragma unroll
+    for (int w = 0; w < 4; ++w) level0[4 * (size_t)j + w] = leaf[w];
+    status[j] = (uint8_t)st;
+  }
+  tree_raise(flag, st);
+}
+// Orders: level 0 already holds ord_new (copied with the update's inputs); item j: range check of the new leaf
+// against p, the tree's current leaf at keys[j] against prev[j] (a stored leaf is below p, so a prev >= p never
+// matches), status[j].
+__global__ void __launch_bounds__(256)
+state_ord_leaf_kernel(const TreeSlot* __restrict__ tab, uint64_t mask, const uint64_t* __restrict__ keys, unsigned cnt,
+                      const uint64_t* __restrict__ empty_leaf, const uint64_t* __restrict__ prev,
+                      const uint64_t* __restrict__ level0, uint8_t* __restrict__ status, unsigned* __restrict__ flag) {
+  const unsigned j = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned st = 0;
+  if (j < cnt) {
+    if (!u256_lt(ld_u256(level0 + 4 * (size_t)j), U256_P)) st |= SP_HASH_OUT_OF_RANGE;
+    if (!tree_leaf_is(tab, mask, keys[j], empty_leaf, prev + 4 * (size_t)j)) st |= SP_STATE_PREV_MISMATCH;
+    status[j] = (uint8_t)st;
+  }
+  tree_raise(flag, st);
+}
 // rehash every ready slot of `old` into `tab`
 __global__ void __launch_bounds__(256)
 tree_rehash_kernel(const TreeSlot* __restrict__ old, uint64_t old_slots, TreeSlot* __restrict__ tab, uint64_t mask) {
@@ -534,25 +595,58 @@ static int tree_root_locked(SparseTree& t, uint64_t* root) {
   return SP_OK;
 }
 
-// The update itself (tree mutex held, context selected).  `may_commit`, when given, is asked once every new
-// node has been hashed and before anything is written to the table: false leaves the tree as it was
-// (*status = SP_TREE_NOT_COMMITTED).
-static int tree_update_locked(SparseTree& t, const uint64_t* keys, const uint64_t* leaves, size_t n, uint64_t* old_root,
-                              uint64_t* new_root, uint8_t* status, const std::function<bool()>* may_commit,
-                              const std::function<void()>* enqueued = nullptr) {
-  const unsigned height = t.height;
+// ---- the update itself, in two phases (tree mutex held, context selected) ----
+//   tree_enqueue   everything up to "levels enqueued" on the tree's stream, and the asynchronous copy-back of the
+//                  status flag and the candidate root;
+//   tree_wait      the ONE wait of an update; hands back the flag;
+//   tree_commit    launches tree_insert_kernel and adopts the candidate root.
+// sp_tree_update and sp_order_batch run them back to back (tree_update_locked); sp_state_batch enqueues two trees,
+// waits for both, decides once and commits both or neither.
+//
+// Level 0 is filled in one of two ways: the host's `leaves` are copied into the work buffer, or a PRODUCER already
+// enqueued on the tree's stream writes the level-0 values there (sp_state_batch: no hash crosses PCIe).  A producer
+// owns `dev_bytes` of the work buffer behind the update's own arrays and `host_bytes` of the tree's page-locked
+// staging buffer behind the update's inputs (host == nullptr: the batch is above PINNED_STAGE_MAX, copy directly).
+struct LeafProducer {
+  size_t dev_bytes = 0, host_bytes = 0;
+  // uploads, and hashing that uses the stream's scratch in a layout of its own: runs first, under the library lock
+  std::function<int(char* dev, char* host, hipStream_t st)> stage;
+  // the leaf kernel and the copy-back of its status bytes: behind tree_reserve's memset / rehash, the copies of keys
+  // and empty roots (d_empty: the empty leaf) and the clearing of `flag`, all on the same stream
+  std::function<int(char* dev, char* host, const TreeSlot* tab, uint64_t mask, const uint64_t* d_keys,
+                    const uint64_t* d_empty, uint64_t* d_level0, unsigned* flag, hipStream_t st)> place;
+};
+struct TreePending {  // what tree_enqueue leaves for tree_wait / tree_commit
+  bool queued = false;  // false: an empty update, nothing is on the stream
+  TreeLevels lv;
+  size_t total = 0;
+  uint64_t* d_felts = nullptr;
+  uint64_t* d_idx = nullptr;
+  const unsigned* h_flag = nullptr;   // where flag and candidate root land: the tree's page-locked buffer, or ...
+  const uint64_t* h_root = nullptr;
+  unsigned flag_host = 0;             // ... these, for an update too large for it
+  uint64_t root_host[4] = {0, 0, 0, 0};
+};
+
+static bool tree_keys_ok(const SparseTree& t, const uint64_t* keys, size_t n) {
   for (size_t i = 0; i < n; ++i) {
-    if (i > 0 && keys[i] <= keys[i - 1]) { set_error("keys must be strictly increasing"); return SP_ERR_BAD_ARGUMENT; }
-    if (height < 64 && (keys[i] >> height) != 0) { set_error("key out of range for height"); return SP_ERR_BAD_ARGUMENT; }
+    if (i > 0 && keys[i] <= keys[i - 1]) { set_error("keys must be strictly increasing"); return false; }
+    if (t.height < 64 && (keys[i] >> t.height) != 0) { set_error("key out of range for height"); return false; }
   }
+  return true;
+}
+
+// `enqueued`, when given, is called once the levels are on the stream and the library lock is free again.
+static int tree_enqueue(SparseTree& t, const uint64_t* keys, const uint64_t* leaves, size_t n, uint64_t* old_root,
+                        uint8_t* status, const LeafProducer* producer, TreePending& p,
+                        const std::function<void()>* enqueued = nullptr) {
+  const unsigned height = t.height;
+  if (!tree_keys_ok(t, keys, n)) return SP_ERR_BAD_ARGUMENT;
   int rc = tree_root_locked(t, old_root);
   if (rc != SP_OK) return rc;
   if (status) *status = 0;
-  if (n == 0) {
-    std::memcpy(new_root, old_root, 32);
-    if (may_commit && !(*may_commit)() && status) *status = SP_TREE_NOT_COMMITTED;
-    return SP_OK;
-  }
+  p.queued = false;
+  if (n == 0) return SP_OK;
   // ---- host: only the node COUNT of every level (merkle_tree.py:18-26 on the keys alone): level l has one node
   // per distinct key >> l, i.e. 1 + the adjacent key pairs whose highest differing bit is >= l ----
   std::vector<size_t> cnt(height + 1);
@@ -568,7 +662,7 @@ static int tree_update_locked(SparseTree& t, const uint64_t* keys, const uint64_
   size_t total = 0;
   for (unsigned l = 0; l <= height; ++l) total += cnt[l];
   // felts: [level 0 values][siblings for level 1's parents][level 1 values][siblings ...] ...
-  TreeLevels lv;
+  TreeLevels& lv = p.lv;
   std::memset(&lv, 0, sizeof(lv));
   lv.height = height;
   size_t felts = 0, idxs = 0, srcs = 0;
@@ -592,7 +686,9 @@ static int tree_update_locked(SparseTree& t, const uint64_t* keys, const uint64_
   tl_mark("tree: table reserved");
   const size_t emp_bytes = ((size_t)height + 1) * 32;
   const size_t felt_bytes = felts * 32, idx_bytes = idxs * 8, src_bytes = srcs * sizeof(int2);
-  SP_HIP(t.buf.reserve(emp_bytes + felt_bytes + idx_bytes + src_bytes + 1024));
+  const size_t own_bytes = emp_bytes + felt_bytes + idx_bytes + src_bytes;
+  const size_t prod_off = (own_bytes + 255) & ~(size_t)255;  // the producer's part of the work buffer
+  SP_HIP(t.buf.reserve(producer ? prod_off + producer->dev_bytes + 1024 : own_bytes + 1024));
   char* b = (char*)t.buf.ptr;
   uint64_t* d_emp = (uint64_t*)b;
   uint64_t* d_felts = (uint64_t*)(b + emp_bytes);
@@ -600,11 +696,31 @@ static int tree_update_locked(SparseTree& t, const uint64_t* keys, const uint64_
   int2* d_src = (int2*)(b + emp_bytes + felt_bytes + idx_bytes);
   hipStream_t st = t.stream;
   Scratch s;
+  unsigned* h_flag = &p.flag_host;
+  uint64_t* h_root = p.root_host;
   {
     // ---- enqueue under the library lock: scratch map, empty-root cache, launch bookkeeping ----
     tl_mark("tree: work buffer ready");
     ctx_lock lk(global_mu());
     tl_mark("tree: library lock taken");
+    // Small updates go through the tree's page-locked buffer (PinnedBuffer): inputs | landing of flag and
+    // candidate root | the producer's part.
+    const size_t leaf_bytes = leaves ? n * 32 : 0;
+    const size_t land_off = (emp_bytes + leaf_bytes + n * 8 + 31) & ~(size_t)31;
+    const size_t in_bytes = land_off + 64 + (producer ? producer->host_bytes : 0);
+    char* stage = nullptr;
+    if (in_bytes <= PINNED_STAGE_MAX && t.hbuf.reserve(in_bytes) == hipSuccess) stage = (char*)t.hbuf.ptr;
+    else (void)hipGetLastError();
+    if (stage) {
+      h_flag = (unsigned*)(stage + land_off);
+      h_root = (uint64_t*)(stage + land_off + 32);
+    }
+    char* prod_host = stage ? stage + land_off + 64 : nullptr;
+    if (producer && producer->stage) {
+      rc = producer->stage(b + prod_off, prod_host, st);
+      if (rc != SP_OK) return rc;
+      tl_mark("tree: producer staged");
+    }
     rc = get_scratch_public(n, s, st);
     if (rc != SP_OK) return rc;
     tl_mark("tree: scratch");
@@ -615,24 +731,25 @@ static int tree_update_locked(SparseTree& t, const uint64_t* keys, const uint64_
     if (rc != SP_OK) return rc;
     tl_mark("tree: empty roots");
     // empty roots + leaves are adjacent in the work buffer (d_emp, then the level-0 values at the start of d_felts):
-    // one copy; the keys a second one.  Small updates go through the tree's page-locked buffer (PinnedBuffer).
-    const size_t in_bytes = emp_bytes + n * 32 + n * 8;
-    char* stage = nullptr;
-    if (in_bytes <= PINNED_STAGE_MAX && t.hbuf.reserve(in_bytes) == hipSuccess) stage = (char*)t.hbuf.ptr;
-    else (void)hipGetLastError();
+    // one copy; the keys a second one.
     if (stage) {
       // the previous update's copies out of this buffer are long finished: every update ends with a wait on `st`
       std::memcpy(stage, emp->data(), emp_bytes);
-      std::memcpy(stage + emp_bytes, leaves, n * 32);
-      std::memcpy(stage + emp_bytes + n * 32, keys, n * 8);
-      SP_HIP(hipMemcpyAsync(d_emp, stage, emp_bytes + n * 32, hipMemcpyHostToDevice, st));
-      SP_HIP(hipMemcpyAsync(d_idx, stage + emp_bytes + n * 32, n * 8, hipMemcpyHostToDevice, st));
+      if (leaves) std::memcpy(stage + emp_bytes, leaves, n * 32);
+      std::memcpy(stage + emp_bytes + leaf_bytes, keys, n * 8);
+      SP_HIP(hipMemcpyAsync(d_emp, stage, emp_bytes + leaf_bytes, hipMemcpyHostToDevice, st));
+      SP_HIP(hipMemcpyAsync(d_idx, stage + emp_bytes + leaf_bytes, n * 8, hipMemcpyHostToDevice, st));
     } else {
       SP_HIP(hipMemcpyAsync(d_emp, emp->data(), emp_bytes, hipMemcpyHostToDevice, st));
-      SP_HIP(hipMemcpyAsync(d_felts, leaves, n * 32, hipMemcpyHostToDevice, st));
+      if (leaves) SP_HIP(hipMemcpyAsync(d_felts, leaves, n * 32, hipMemcpyHostToDevice, st));
       SP_HIP(hipMemcpyAsync(d_idx, keys, n * 8, hipMemcpyHostToDevice, st));
     }
     tl_mark("tree: inputs copied");
+    if (producer && producer->place) {  // level 0 comes from (or is checked by) a kernel on this stream
+      rc = producer->place(b + prod_off, prod_host, t.table, t.slots - 1, d_idx, d_emp, d_felts, s.flag, st);
+      if (rc != SP_OK) return rc;
+      tl_mark("tree: leaf kernel enqueued");
+    }
     // the structure of every level and the sibling lookups, then the hashes level by level
     hipLaunchKernelGGL(tree_level_nodes_kernel, dim3(height), dim3(1024), 0, st, lv, d_idx, d_idx);
     hipLaunchKernelGGL(tree_children_kernel, dim3((unsigned)((total - cnt[height] + 255) / 256)), dim3(256), 0, st, lv,
@@ -674,13 +791,62 @@ static int tree_update_locked(SparseTree& t, const uint64_t* keys, const uint64_
   tl_mark("tree: levels enqueued");
   if (enqueued) (*enqueued)();  // the library lock is free again: sp_order_batch lets its verifier through
   // ---- the device runs; nobody waits on the library lock for it ----
-  // The status flag and the candidate root come back together: ONE wait per update.
-  unsigned f = 0;
-  uint64_t candidate[4];
-  SP_HIP(hipMemcpyAsync(&f, s.flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  SP_HIP(hipMemcpyAsync(candidate, d_felts + 4 * (size_t)lv.val_base[height], 32, hipMemcpyDeviceToHost, st));
-  SP_HIP(hipStreamSynchronize(st));
+  // The status flag and the candidate root come back together: ONE wait per update (tree_wait).
+  p.queued = true;  // from here on the stream holds work that reads the tree's buffers
+  p.total = total;
+  p.d_felts = d_felts;
+  p.d_idx = d_idx;
+  p.h_flag = h_flag;
+  p.h_root = h_root;
+  SP_HIP(hipMemcpyAsync(h_flag, s.flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  SP_HIP(hipMemcpyAsync(h_root, d_felts + 4 * (size_t)lv.val_base[height], 32, hipMemcpyDeviceToHost, st));
+  return SP_OK;
+}
+
+// Waits for what tree_enqueue put on the stream; *flag = the update's status flag (0 for an empty update).
+static int tree_wait(SparseTree& t, const TreePending& p, unsigned* flag) {
+  *flag = 0;
+  if (!p.queued) return SP_OK;
+  SP_HIP(hipStreamSynchronize(t.stream));
   tl_mark("tree: levels hashed");
+  *flag = *p.h_flag;
+  return SP_OK;
+}
+
+// commit: every new node into the table, one launch - and nobody waits for it.  The tree's next
+// operation is ordered behind it on the tree's stream (lookups, the next update's copies into the work
+// buffer, the rehash of a growing table); a reallocation of the work buffer or sp_tree_destroy synchronise
+// (hipFree / tree_free).  ~0.09 ms of 217 k hash-table insertions leave the caller's latency.
+static int tree_commit(SparseTree& t, const TreePending& p, uint64_t* new_root) {
+  hipLaunchKernelGGL(tree_insert_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, t.stream, t.table,
+                     t.slots - 1, p.lv, p.d_idx, p.d_felts, (unsigned)p.total, t.d_entries);
+  SP_HIP(hipGetLastError());
+  std::memcpy(t.root, p.h_root, 32);
+  t.has_root = true;
+  t.entries += p.total;  // upper bound until tree_reserve reads the device counter again
+  std::memcpy(new_root, t.root, 32);
+  return SP_OK;
+}
+
+// One tree, the phases back to back.  `may_commit`, when given, is asked once every new node has been hashed and
+// before anything is written to the table: false leaves the tree as it was (*status = SP_TREE_NOT_COMMITTED).
+static int tree_update_locked(SparseTree& t, const uint64_t* keys, const uint64_t* leaves, size_t n, uint64_t* old_root,
+                              uint64_t* new_root, uint8_t* status, const std::function<bool()>* may_commit,
+                              const std::function<void()>* enqueued = nullptr) {
+  TreePending p;
+  int rc = tree_enqueue(t, keys, leaves, n, old_root, status, nullptr, p, enqueued);
+  if (rc != SP_OK) {
+    if (p.queued) (void)hipStreamSynchronize(t.stream);  // the copy-back failed: nothing may still run on `p`
+    return rc;
+  }
+  if (!p.queued) {
+    std::memcpy(new_root, old_root, 32);
+    if (may_commit && !(*may_commit)() && status) *status = SP_TREE_NOT_COMMITTED;
+    return SP_OK;
+  }
+  unsigned f = 0;
+  rc = tree_wait(t, p, &f);
+  if (rc != SP_OK) return rc;
   if (status) *status = (uint8_t)f;
   if (f != 0) {  // an input out of range or an unhashable pair: nothing was written, the tree is as it was
     std::memcpy(new_root, old_root, 32);
@@ -691,18 +857,7 @@ static int tree_update_locked(SparseTree& t, const uint64_t* keys, const uint64_
     std::memcpy(new_root, old_root, 32);
     return SP_OK;
   }
-  // ---- commit: every new node into the table, one launch - and nobody waits for it.  The tree's next
-  // operation is ordered behind it on the tree's stream (lookups, the next update's copies into the work
-  // buffer, the rehash of a growing table); a reallocation of the work buffer or sp_tree_destroy synchronise
-  // (hipFree / tree_free).  ~0.09 ms of 217 k hash-table insertions leave the caller's latency.
-  hipLaunchKernelGGL(tree_insert_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, t.table, t.slots - 1, lv,
-                     d_idx, d_felts, (unsigned)total, t.d_entries);
-  SP_HIP(hipGetLastError());
-  std::memcpy(t.root, candidate, 32);
-  t.has_root = true;
-  t.entries += total;  // upper bound until tree_reserve reads the device counter again
-  std::memcpy(new_root, t.root, 32);
-  return SP_OK;
+  return tree_commit(t, p, new_root);
 }
 
 namespace sp {
@@ -932,6 +1087,183 @@ int sp_order_batch(const uint64_t* words, size_t depth, size_t n, const uint64_t
   // when both legs failed the tree's code wins and the text is whichever leg failed last
   if (rc != SP_OK) return rc;
   return vrc;
+}
+
+
+// shared_state_apply_state_updates (services/perpetual/cairo/state/state.cairo:135-186) in ONE call: the previous and
+// the new leaf of every touched position (position/hash.cairo:76-131), merkle_multi_update of the positions tree
+// (:155-161) and of the orders tree (:167-173), all or nothing across both.  Stages:
+//   positions tree's stream   words of all previous chains and of the changed new chains -> work buffer; ONE
+//                             enqueue_pedersen_chain_ragged over both halves (it slices above its launch cap);
+//                             state_pos_leaf_kernel: current leaf against previous hash, status byte, level 0;
+//                             then the update's structure kernels and level launches (tree_enqueue)
+//   orders tree's stream      ord_new into level 0, ord_prev beside it; state_ord_leaf_kernel; structure, levels
+//   host                      waits for both streams, decides ONCE, launches both insert kernels or neither
+// Nothing returns to the host between the stages and no hash crosses PCIe.  Both tree mutexes are held from start to
+// end, taken in ascending handle order; the library lock only inside tree_enqueue; no host lane, no thread.
+int sp_state_batch(int positions_tree, int orders_tree, const uint64_t* pos_keys, size_t n_pos,
+                   const uint64_t* prev_words, const uint32_t* prev_off, const uint64_t* new_words,
+                   const uint32_t* new_off, const uint64_t* ord_keys, const uint64_t* ord_prev,
+                   const uint64_t* ord_new, size_t n_ord, uint64_t* pos_old_root, uint64_t* pos_new_root,
+                   uint64_t* ord_old_root, uint64_t* ord_new_root, uint8_t* pos_status, uint8_t* ord_status,
+                   uint8_t* batch_status) {
+  SP_REQUIRE_READY();
+  if (!batch_status || !pos_old_root || !pos_new_root || !ord_old_root || !ord_new_root) {
+    set_error("sp_state_batch: the four roots and batch_status are required");
+    return SP_ERR_BAD_ARGUMENT;
+  }
+  if ((n_pos && (!pos_keys || !prev_words || !prev_off || !new_off)) || (n_ord && (!ord_keys || !ord_prev || !ord_new))) {
+    set_error("sp_state_batch: null input array");
+    return SP_ERR_BAD_ARGUMENT;
+  }
+  if (positions_tree == orders_tree) { set_error("sp_state_batch: the same tree handle twice"); return SP_ERR_BAD_ARGUMENT; }
+  TimelineScope timeline("sp_state_batch");
+  // ---- offsets: the previous chains as sp_pedersen_chains_ragged wants them, the new ones may be empty ----
+  size_t n_changed = 0;
+  if (n_pos) {
+    if (n_pos >= 0x7fffffffull) { set_error("sp_state_batch: too many positions"); return SP_ERR_BAD_ARGUMENT; }
+    if (prev_off[0] != 0 || new_off[0] != 0) { set_error("sp_state_batch: off[0] must be 0"); return SP_ERR_BAD_ARGUMENT; }
+    for (size_t i = 0; i < n_pos; ++i) {
+      if (prev_off[i + 1] <= prev_off[i]) {
+        set_error("sp_state_batch: every previous chain needs at least one element");
+        return SP_ERR_BAD_ARGUMENT;
+      }
+      if (new_off[i + 1] < new_off[i]) { set_error("sp_state_batch: decreasing offset"); return SP_ERR_BAD_ARGUMENT; }
+      n_changed += new_off[i + 1] != new_off[i];
+    }
+    if ((uint64_t)prev_off[n_pos] + new_off[n_pos] > 0xffffffffull) {
+      set_error("sp_state_batch: more than 2^32 words");
+      return SP_ERR_BAD_ARGUMENT;
+    }
+    if (new_off[n_pos] && !new_words) { set_error("sp_state_batch: null input array"); return SP_ERR_BAD_ARGUMENT; }
+  }
+  if (n_ord >= 0x7fffffffull) { set_error("sp_state_batch: too many orders"); return SP_ERR_BAD_ARGUMENT; }
+  // ---- both trees, locked in ascending handle order whichever role they play ----
+  TreeScope first, second;
+  const bool pos_first = positions_tree < orders_tree;
+  int rc = first.open(pos_first ? positions_tree : orders_tree);
+  if (rc != SP_OK) return rc;
+  rc = second.open(pos_first ? orders_tree : positions_tree);
+  if (rc != SP_OK) return rc;
+  SparseTree& P = pos_first ? *first.t : *second.t;
+  SparseTree& O = pos_first ? *second.t : *first.t;
+  if (P.ctx_index != O.ctx_index) {
+    set_error("sp_state_batch: the two trees live on different contexts");
+    return SP_ERR_BAD_ARGUMENT;
+  }
+  if (!tree_keys_ok(P, pos_keys, n_pos) || !tree_keys_ok(O, ord_keys, n_ord)) return SP_ERR_BAD_ARGUMENT;
+  tl_mark("trees locked, arguments checked");
+
+  // ---- positions: previous chains, then the changed new ones, as one ragged batch ----
+  const size_t n_chains = n_pos + n_changed;
+  const size_t prev_total = n_pos ? prev_off[n_pos] : 0, new_total = n_pos ? new_off[n_pos] : 0;
+  std::vector<uint32_t> chain_off(n_chains + 1, 0), map(n_pos);
+  for (size_t i = 0, k = 0; i < n_pos; ++i) {
+    chain_off[i + 1] = prev_off[i + 1];
+    const bool changed = new_off[i + 1] != new_off[i];
+    map[i] = changed ? (uint32_t)k : STATE_UNCHANGED;
+    if (changed) chain_off[n_pos + ++k] = (uint32_t)(prev_total + new_off[i + 1]);
+  }
+  auto pad = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  std::vector<uint8_t> pos_land, ord_land;  // landing of the status bytes when the page-locked buffer is not used
+  LeafProducer pp;
+  const size_t p_words = (prev_total + new_total) * 32;
+  const size_t pd_hash = pad(p_words), pd_map = pd_hash + pad(n_chains * 32), pd_cst = pd_map + pad(n_pos * 4),
+               pd_st = pd_cst + pad(n_chains);
+  const size_t ph_map = p_words, ph_st = p_words + pad(n_pos * 4);
+  pp.dev_bytes = pd_st + pad(n_pos);
+  pp.host_bytes = ph_st + n_pos;
+  const uint8_t* pos_bytes = nullptr;
+  pp.stage = [&](char* dev, char* host, hipStream_t st) -> int {
+    if (host) {
+      std::memcpy(host, prev_words, prev_total * 32);
+      if (new_total) std::memcpy(host + prev_total * 32, new_words, new_total * 32);
+      std::memcpy(host + ph_map, map.data(), n_pos * 4);
+      SP_HIP(hipMemcpyAsync(dev, host, p_words, hipMemcpyHostToDevice, st));
+      SP_HIP(hipMemcpyAsync(dev + pd_map, host + ph_map, n_pos * 4, hipMemcpyHostToDevice, st));
+    } else {
+      SP_HIP(hipMemcpyAsync(dev, prev_words, prev_total * 32, hipMemcpyHostToDevice, st));
+      if (new_total) SP_HIP(hipMemcpyAsync(dev + prev_total * 32, new_words, new_total * 32, hipMemcpyHostToDevice, st));
+      SP_HIP(hipMemcpyAsync(dev + pd_map, map.data(), n_pos * 4, hipMemcpyHostToDevice, st));
+    }
+    return enqueue_pedersen_chain_ragged((const uint64_t*)dev, chain_off.data(), n_chains, (uint64_t*)(dev + pd_hash),
+                                         (uint8_t*)(dev + pd_cst), st);
+  };
+  pp.place = [&](char* dev, char* host, const TreeSlot* tab, uint64_t mask, const uint64_t* d_keys, const uint64_t* d_empty,
+                 uint64_t* d_level0, unsigned* flag, hipStream_t st) -> int {
+    hipLaunchKernelGGL(state_pos_leaf_kernel, dim3((unsigned)((n_pos + 255) / 256)), dim3(256), 0, st, tab, mask, d_keys,
+                       (unsigned)n_pos, d_empty, (const uint64_t*)(dev + pd_hash), (const uint8_t*)(dev + pd_cst),
+                       (const uint32_t*)(dev + pd_map), d_level0, (uint8_t*)(dev + pd_st), flag);
+    SP_HIP(hipGetLastError());
+    uint8_t* land = host ? (uint8_t*)(host + ph_st) : (pos_land.resize(n_pos), pos_land.data());
+    pos_bytes = land;
+    SP_HIP(hipMemcpyAsync(land, dev + pd_st, n_pos, hipMemcpyDeviceToHost, st));
+    return SP_OK;
+  };
+  // ---- orders: the new leaves go to level 0 with the update's inputs, the previous ones beside them ----
+  LeafProducer op;
+  const size_t od_st = pad(n_ord * 32);
+  op.dev_bytes = od_st + pad(n_ord);
+  op.host_bytes = n_ord * 32 + n_ord;
+  const uint8_t* ord_bytes = nullptr;
+  op.stage = [&](char* dev, char* host, hipStream_t st) -> int {
+    if (host) std::memcpy(host, ord_prev, n_ord * 32);
+    SP_HIP(hipMemcpyAsync(dev, host ? (const void*)host : (const void*)ord_prev, n_ord * 32, hipMemcpyHostToDevice, st));
+    return SP_OK;
+  };
+  op.place = [&](char* dev, char* host, const TreeSlot* tab, uint64_t mask, const uint64_t* d_keys, const uint64_t* d_empty,
+                 uint64_t* d_level0, unsigned* flag, hipStream_t st) -> int {
+    hipLaunchKernelGGL(state_ord_leaf_kernel, dim3((unsigned)((n_ord + 255) / 256)), dim3(256), 0, st, tab, mask, d_keys,
+                       (unsigned)n_ord, d_empty, (const uint64_t*)dev, d_level0, (uint8_t*)(dev + od_st), flag);
+    SP_HIP(hipGetLastError());
+    uint8_t* land = host ? (uint8_t*)(host + n_ord * 32) : (ord_land.resize(n_ord), ord_land.data());
+    ord_bytes = land;
+    SP_HIP(hipMemcpyAsync(land, dev + od_st, n_ord, hipMemcpyDeviceToHost, st));
+    return SP_OK;
+  };
+
+  // ---- enqueue both (each tree on its own stream: the two level sequences run side by side), wait for both ----
+  TreePending pend_p, pend_o;
+  uint64_t p_old[4], o_old[4];
+  rc = tree_enqueue(P, pos_keys, nullptr, n_pos, p_old, nullptr, &pp, pend_p);
+  tl_mark("positions enqueued");
+  int rc2 = SP_OK;
+  if (rc == SP_OK) {
+    rc2 = tree_enqueue(O, ord_keys, ord_new, n_ord, o_old, nullptr, &op, pend_o);
+    tl_mark("orders enqueued");
+  }
+  if (rc != SP_OK || rc2 != SP_OK) {  // whatever did get onto a stream reads this call's buffers: drain it
+    if (P.stream) (void)hipStreamSynchronize(P.stream);
+    if (O.stream) (void)hipStreamSynchronize(O.stream);
+    return rc != SP_OK ? rc : rc2;
+  }
+  unsigned flag_p = 0, flag_o = 0;
+  rc = tree_wait(P, pend_p, &flag_p);
+  rc2 = tree_wait(O, pend_o, &flag_o);
+  if (rc != SP_OK || rc2 != SP_OK) {
+    if (O.stream) (void)hipStreamSynchronize(O.stream);
+    return rc != SP_OK ? rc : rc2;
+  }
+  tl_mark("both trees hashed");
+  // ---- decide once: the item status bytes are in the flags already (the leaf kernels raise what they write) ----
+  const unsigned bad = flag_p | flag_o;
+  uint64_t p_new[4], o_new[4];
+  std::memcpy(p_new, p_old, 32);
+  std::memcpy(o_new, o_old, 32);
+  if (bad == 0) {
+    if (pend_p.queued) rc = tree_commit(P, pend_p, p_new);
+    if (rc == SP_OK && pend_o.queued) rc = tree_commit(O, pend_o, o_new);
+    if (rc != SP_OK) return rc;
+    tl_mark("both trees committed");
+  }
+  if (pos_status && n_pos) std::memcpy(pos_status, pos_bytes, n_pos);
+  if (ord_status && n_ord) std::memcpy(ord_status, ord_bytes, n_ord);
+  std::memcpy(pos_old_root, p_old, 32);
+  std::memcpy(pos_new_root, p_new, 32);
+  std::memcpy(ord_old_root, o_old, 32);
+  std::memcpy(ord_new_root, o_new, 32);
+  *batch_status = bad ? (uint8_t)(SP_TREE_NOT_COMMITTED | (bad & 0x7f)) : 0;
+  return SP_OK;
 }
 
 }  // extern "C"

@@ -221,3 +221,43 @@ def order_batch(words, r, s, qx, tree, leaves, qy=None, id_shift=187):
     if st[0] & (HASH_OUT_OF_RANGE | HASH_UNHASHABLE):
         _raise_hash_status(HASH_UNHASHABLE if st[0] & 2 else HASH_OUT_OF_RANGE)
     return z, verdicts, _lib.unpack_felts(old, 1)[0], _lib.unpack_felts(new, 1)[0], st[0] == 0
+
+
+STATE_PREV_MISMATCH = 0x10  # include/starkperp.h SP_STATE_PREV_MISMATCH
+
+
+def state_batch(positions_tree, orders_tree, pos_keys, prev_words, prev_off, new_words, new_off, ord_keys, ord_prev,
+                ord_new):
+    """The whole state update of a batch in ONE library call (sp_state_batch; state/state.cairo:135-186): previous and
+    new leaf of every touched position, update of the positions tree and of the orders tree (state.LibrarySparseTree
+    both), all or nothing across the two.
+      pos_keys uint64[n_pos], ord_keys uint64[n_ord]   strictly increasing, squashed (state.squash_updates)
+      prev_words uint64[*, 4], prev_off uint32[n_pos + 1]   the previous leaf of position i is the left-fold chain over
+                 rows prev_off[i] .. prev_off[i + 1] (the convention of pedersen_chains_ragged)
+      new_words, new_off   the new leaf likewise; new_off[i + 1] == new_off[i]: the position is unchanged
+      ord_prev, ord_new uint64[n_ord, 4]   the orders-tree leaves before and after
+    state.pack_state_batch builds these arrays from squashed updates.  Nothing is raised for data-dependent outcomes:
+    returns ((pos_old_root, pos_new_root), (ord_old_root, ord_new_root), pos_status uint8[n_pos], ord_status
+    uint8[n_ord], batch_status) - batch_status 0 = committed, otherwise TREE_NOT_COMMITTED | the status bits met
+    (HASH_OUT_OF_RANGE, HASH_UNHASHABLE, STATE_PREV_MISMATCH) with both trees as they were."""
+    pos_keys = np.ascontiguousarray(pos_keys, dtype=np.uint64)
+    ord_keys = np.ascontiguousarray(ord_keys, dtype=np.uint64)
+    prev_off = np.ascontiguousarray(prev_off, dtype=np.uint32)
+    new_off = np.ascontiguousarray(new_off, dtype=np.uint32)
+    assert pos_keys.ndim == 1 and ord_keys.ndim == 1 and prev_off.ndim == 1 and new_off.ndim == 1
+    n_pos, n_ord = pos_keys.shape[0], ord_keys.shape[0]
+    assert prev_off.shape[0] == n_pos + 1 and new_off.shape[0] == n_pos + 1, "offsets are uint32[n_pos + 1]"
+    prev_words, new_words = _felts(prev_words), _felts(new_words)
+    assert int(prev_off[-1]) <= prev_words.shape[0] and int(new_off[-1]) <= new_words.shape[0], \
+        "offsets point behind the words"
+    ord_prev, ord_new = _felts(ord_prev, n_ord), _felts(ord_new, n_ord)
+    roots = np.zeros((4, 4), dtype=np.uint64)
+    pos_st, ord_st = np.zeros(n_pos, dtype=np.uint8), np.zeros(n_ord, dtype=np.uint8)
+    batch_st = np.zeros(1, dtype=np.uint8)
+    _lib.check(_lib.ensure_init().sp_state_batch(
+        positions_tree._handle, orders_tree._handle, _ptr(pos_keys), n_pos, _ptr(prev_words), _ptr(prev_off),
+        _ptr(new_words), _ptr(new_off), _ptr(ord_keys), _ptr(ord_prev), _ptr(ord_new), n_ord, _ptr(roots[0:1]),
+        _ptr(roots[1:2]), _ptr(roots[2:3]), _ptr(roots[3:4]), _ptr(pos_st), _ptr(ord_st), _ptr(batch_st)),
+        "sp_state_batch")
+    r = ints_from_felts(roots)
+    return (r[0], r[1]), (r[2], r[3]), pos_st, ord_st, int(batch_st[0])

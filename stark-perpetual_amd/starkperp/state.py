@@ -230,6 +230,31 @@ def hash_position_updates(updates: Sequence[Tuple[int, Position, Position]]):
     return out
 
 
+def pack_state_batch(pos_updates: Sequence[Tuple[int, Position, Position]],
+                     order_updates: Sequence[Tuple[int, int, int]]):
+    """Squashed updates -> the arrays of batch_np.state_batch / sp_state_batch (pure host code, no GPU):
+    pos_updates (key, previous Position, new Position) and order_updates (key, previous leaf, new leaf), both sorted
+    by key (squash_updates).  Returns (pos_keys uint64[n_pos], prev_words uint64[*, 4], prev_off uint32[n_pos + 1],
+    new_words uint64[*, 4], new_off uint32[n_pos + 1], ord_keys uint64[n_ord], ord_prev uint64[n_ord, 4], ord_new
+    uint64[n_ord, 4]): the words of position_words chain after chain; an unchanged position (hash.cairo:76-131: it is
+    hashed once) gives a new chain of length zero, new_off[i + 1] == new_off[i]."""
+    import numpy as np
+    from .batch_np import felts_from_ints
+    n_pos = len(pos_updates)
+    prev_flat, new_flat = [], []
+    prev_off, new_off = np.zeros(n_pos + 1, dtype=np.uint32), np.zeros(n_pos + 1, dtype=np.uint32)
+    for i, (_, prev, new) in enumerate(pos_updates):
+        prev_flat.extend(position_words(prev))
+        prev_off[i + 1] = len(prev_flat)
+        if prev != new:
+            new_flat.extend(position_words(new))
+        new_off[i + 1] = len(new_flat)
+    felts = lambda values: felts_from_ints(values) if values else np.zeros((0, 4), dtype=np.uint64)
+    return (np.array([k for k, _, _ in pos_updates], dtype=np.uint64), felts(prev_flat), prev_off, felts(new_flat),
+            new_off, np.array([k for k, _, _ in order_updates], dtype=np.uint64),
+            felts([p for _, p, _ in order_updates]), felts([q for _, _, q in order_updates]))
+
+
 # ---- the per-batch state-root update ------------------------------------------------------------
 def squash_updates(accesses: Sequence[Tuple[int, object, object]]):
     """squash_dict semantics (state/state.cairo:67-96): a chronological list of
@@ -274,7 +299,48 @@ class SharedState:
     def apply_state_updates(self, position_accesses, order_accesses):
         """shared_state_apply_state_updates (state/state.cairo:135-186): squash, hash the previous
         and new positions (hash_position_updates), check the previous leaves against the tree,
-        merkle-multi-update both trees.  Returns ((old_pos_root, new_pos_root), (old_ord, new_ord))."""
+        merkle-multi-update both trees.  Returns ((old_pos_root, new_pos_root), (old_ord, new_ord)).
+        When the library keeps both trees and hashes the positions, all of it is ONE library call (sp_state_batch,
+        _apply_in_one_call); with an injected hash the steps are separate calls (_apply_in_separate_calls)."""
+        if (isinstance(self.positions, LibrarySparseTree) and isinstance(self.orders, LibrarySparseTree)
+                and self._position_hashes is position_hashes_many):
+            return self._apply_in_one_call(position_accesses, order_accesses)
+        return self._apply_in_separate_calls(position_accesses, order_accesses)
+
+    def _apply_in_one_call(self, position_accesses, order_accesses):
+        """Through sp_state_batch: the previous-leaf checks, both trees' hashing and the all-or-nothing decision
+        happen on the device; the status bytes are turned into the assertions of the separate-call route."""
+        from . import batch_np
+        pos = squash_updates(position_accesses)
+        orders = squash_updates(order_accesses)
+        for key, _, _ in pos:
+            assert 0 <= key < (1 << self.positions.height)
+        for key, _, new in orders:
+            assert 0 <= key < (1 << self.orders.height) and 0 <= new < batch.FIELD_PRIME, \
+                "order leaf out of range"
+        # (a previous value that is no field element cannot be what a tree holds, nor be packed into a felt)
+        assert all(0 <= prev < batch.FIELD_PRIME for _, prev, _ in orders), \
+            "previous order state does not match the tree"
+        pos_roots, ord_roots, pos_st, ord_st, batch_st = batch_np.state_batch(
+            self.positions, self.orders, *pack_state_batch(pos, orders))
+        if batch_st == 0:
+            return pos_roots, ord_roots
+        hashing = batch.HASH_OUT_OF_RANGE | batch.HASH_UNHASHABLE
+        for code in pos_st:  # a position word out of range / an unhashable step: what the chain call raises
+            if code & hashing:
+                batch._raise_hash_status(batch.HASH_UNHASHABLE if code & batch.HASH_UNHASHABLE
+                                         else batch.HASH_OUT_OF_RANGE)
+        assert not any(code & batch_np.STATE_PREV_MISMATCH for code in pos_st), \
+            "previous position does not match the tree"
+        assert not any(code & batch_np.STATE_PREV_MISMATCH for code in ord_st), \
+            "previous order state does not match the tree"
+        assert not any(code & batch.HASH_OUT_OF_RANGE for code in ord_st), "order leaf out of range"
+        # what is left was raised by the level hashing of one of the trees
+        raise AssertionError("Unhashable input." if batch_st & batch.HASH_UNHASHABLE else "leaf out of range")
+
+    def _apply_in_separate_calls(self, position_accesses, order_accesses):
+        """The same step as separate calls: two position-hash calls, two previous-leaf reads, the two tree updates
+        one after the other and a third update to roll the first back when the second fails."""
         # Every precondition first - the Cairo twin fails the whole batch, so nothing may be written
         # before both access lists have been squashed and checked against both trees.
         pos = squash_updates(position_accesses)

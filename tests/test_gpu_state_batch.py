@@ -1,0 +1,483 @@
+"""sp_state_batch (include/starkperp.h): the whole state update of a batch - previous and new position leaves, the
+positions tree and the orders tree, all or nothing - in one library call, through starkperp.batch_np and ctypes.
+
+Expected values: the oracle twin SharedState(h1, h2, hash_many=<C oracle hash>, position_hashes=<R.position_hash>)
+(host bookkeeping of starkperp.state with the oracle's hashes) and, from scratch, R.merkle_multi_update_sparse over
+everything written so far.  R.position_hash does the packing of every position leaf; its hashes and the tree's go
+through oracle/starkref.c in batches (the pure-Python hash takes 17 ms: a few positions per case are checked against
+it as well)."""
+import ctypes
+import os
+import random
+import subprocess
+import sys
+import textwrap
+import threading
+
+import numpy as np
+import pytest
+
+from oracle import cref
+from oracle import ref_py as R
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P = R.FIELD_PRIME
+EMPTY = (0, 0, ())
+NOT_COMMITTED, PREV_MISMATCH, OUT_OF_RANGE = 0x80, 0x10, 1
+BAD_ARGUMENT = -3
+
+
+# ---- the oracle side -------------------------------------------------------------------------------
+def oracle_hash_many(xs, ys):
+    return cref.opt_pedersen_hash_many(list(xs), list(ys))[0]
+
+
+_memo = {}
+
+
+def oracle_hash(x, y):
+    """The C oracle's hash, one pair; remembers what the twin's level calls have computed (oracle_hash_many_memo)."""
+    if (x, y) not in _memo:
+        _memo[(x, y)] = oracle_hash_many([x], [y])[0]
+    return _memo[(x, y)]
+
+
+def oracle_hash_many_memo(xs, ys):
+    out = oracle_hash_many(xs, ys)
+    _memo.update(zip(zip(xs, ys), out))
+    return out
+
+
+def oracle_position_hashes(positions):
+    """R.position_hash for many positions: the oracle's own packing (its hash_function hook records the words), the
+    chains folded in lockstep through the C oracle."""
+    chains = []
+    for p in positions:
+        words = [0]
+        R.position_hash(p[0], p[1], list(p[2]), hash_function=lambda acc, w, words=words: words.append(w) or 0)
+        chains.append(words)
+    acc = [c[0] for c in chains]
+    for step in range(1, max([len(c) for c in chains], default=0)):
+        live = [i for i, c in enumerate(chains) if len(c) > step]
+        for i, h in zip(live, oracle_hash_many([acc[i] for i in live], [chains[i][step] for i in live])):
+            acc[i] = h
+    return acc
+
+
+def test_oracle_helpers_agree_with_the_pure_python_oracle():
+    rng = random.Random(2)
+    poss = [random_position(rng, n) for n in (0, 3, 6)]
+    assert oracle_position_hashes(poss) == [R.position_hash(p[0], p[1], list(p[2])) for p in poss]
+    assert oracle_hash(3, 4) == R.pedersen_hash(3, 4)
+
+
+def random_position(rng, n_assets):
+    ids = set()
+    while len(ids) < n_assets:
+        ids.add(rng.randrange(1, 2**120))
+    ids = sorted(ids)
+    assets = tuple((a, rng.randrange(-(2**63), 2**63), rng.randrange(-(2**63), 2**63)) for a in ids)
+    return (rng.randrange(2**251), rng.randrange(-(2**63), 2**63), assets)
+
+
+# ---- the two sides of one state ---------------------------------------------------------------------
+class Pair:
+    """The library's two trees and the oracle twin, with the Python-side record of what they hold."""
+
+    def __init__(self, h_pos, h_ord):
+        from starkperp import state
+        self.state = state
+        self.h_pos, self.h_ord = h_pos, h_ord
+        self.twin = state.SharedState(h_pos, h_ord, hash_many=oracle_hash_many_memo,
+                                      position_hashes=oracle_position_hashes)
+        self.empty_leaf = oracle_position_hashes([EMPTY])[0]
+        self.ptree = state.LibrarySparseTree(h_pos, self.empty_leaf)
+        self.otree = state.LibrarySparseTree(h_ord, 0)
+        self.pos, self.ord = {}, {}  # key -> Position / leaf
+
+    def close(self):
+        self.ptree.close(), self.otree.close()
+
+    def roots(self):
+        return self.ptree.root, self.otree.root
+
+    def call(self, arrays):
+        from starkperp import batch_np
+        return batch_np.state_batch(self.ptree, self.otree, *arrays)
+
+    def make_batch(self, rng, n_pos, n_ord, mode, forced_pos=(), forced_ord=()):
+        """Squashed updates that continue from the state: the forced keys, one overwritten key and one sibling k ^ 1
+        of a written key whenever there is state and room, then overwritten keys, siblings and fresh keys at random;
+        asset counts 0..6 in rotation; mode all / none / alternating = which positions change."""
+        def keys(known, height, n, forced):
+            out = set(forced)
+            room = min(n, 2**height)
+            assert len(out) <= room
+            if known and room - len(out) >= 2:
+                out.add(rng.choice(sorted(known)))
+                out.add(rng.choice(sorted(known)) ^ 1)
+            while len(out) < room:
+                c = rng.random()
+                if known and c < 0.3:
+                    out.add(rng.choice(sorted(known)))
+                elif known and c < 0.55:
+                    out.add(rng.choice(sorted(known)) ^ 1)
+                else:
+                    out.add(rng.randrange(2**height))
+            return sorted(out)
+        pos = []
+        for i, k in enumerate(keys(self.pos, self.h_pos, n_pos, forced_pos)):
+            prev = self.pos.get(k, EMPTY)
+            changed = mode == "all" or (mode == "alternating" and i % 2 == 0)
+            pos.append((k, prev, random_position(rng, (i + len(self.pos)) % 7) if changed else prev))
+        orders = [(k, self.ord.get(k, 0), rng.randrange(P)) for k in keys(self.ord, self.h_ord, n_ord, forced_ord)]
+        return pos, orders
+
+    def expect_commit(self, pos, orders):
+        """Runs the batch on both sides and checks roots, status and probed leaves."""
+        rng = random.Random(len(self.pos) + 7 * len(self.ord))
+        want = self.twin.apply_state_updates(pos, orders)
+        p_roots, o_roots, p_st, o_st, b_st = self.call(self.state.pack_state_batch(pos, orders))
+        assert (p_roots, o_roots) == want
+        assert b_st == 0 and not p_st.any() and not o_st.any()
+        assert p_st.shape == (len(pos),) and o_st.shape == (len(orders),)
+        self.pos.update({k: q for k, _, q in pos})
+        self.ord.update({k: q for k, _, q in orders})
+        assert self.roots() == (want[0][1], want[1][1])
+        self.check_leaves(rng)
+
+    def check_leaves(self, rng):
+        for tree, ref, known, height in ((self.ptree, self.twin.positions, self.pos, self.h_pos),
+                                         (self.otree, self.twin.orders, self.ord, self.h_ord)):
+            probe = rng.sample(sorted(known), min(len(known), 8)) + [rng.randrange(2**height), 0, 2**height - 1]
+            assert tree.get_many(probe) == ref.get_many(probe)
+
+    def check_from_scratch(self):
+        """The roots once more, by the oracle's own sparse-tree walk over everything written (no SharedState /
+        squash code involved)."""
+        leaves = dict(zip(self.pos, oracle_position_hashes(list(self.pos.values()))))
+        assert self.ptree.root == R.merkle_multi_update_sparse(self.h_pos, leaves, self.empty_leaf, oracle_hash)
+        assert self.otree.root == R.merkle_multi_update_sparse(self.h_ord, self.ord, 0, oracle_hash)
+
+
+# (heights), then per batch: (n_pos, n_ord, which positions change)
+SEQUENCES = [
+    ((3, 3), [(5, 3, "all"), (2, 1, "none"), (0, 3, "all"), (5, 0, "alternating")]),
+    ((16, 8), [(150, 150, "all"), (150, 0, "alternating"), (0, 0, "all"), (1, 1, "none")]),
+    ((64, 64), [(150, 150, "all"), (5, 3, "alternating"), (2, 0, "none"), (0, 1, "all")]),
+]
+
+
+@pytest.mark.parametrize("heights,batches", SEQUENCES, ids=["h3_3", "h16_8", "h64_64"])
+def test_state_batch_matches_the_oracle_over_a_sequence_of_batches(heights, batches):
+    rng = random.Random(100 + heights[0])
+    pair = Pair(*heights)
+    assert pair.roots() == (pair.twin.positions_root, pair.twin.orders_root)
+    for r, (n_pos, n_ord, mode) in enumerate(batches):
+        forced_pos = (0, 2**heights[0] - 1, 4, 5) if r == 0 else ()
+        forced_ord = (0, 2**heights[1] - 1, 2**heights[1] - 2) if r == 0 else ()
+        pos, orders = pair.make_batch(rng, n_pos, n_ord, mode, forced_pos, forced_ord)
+        assert len(pos) == min(n_pos, 2**heights[0]) and len(orders) == min(n_ord, 2**heights[1])
+        if r > 0 and n_pos >= 2:  # later batches continue from state: an overwritten key is among them
+            assert any(k in pair.pos for k, _, _ in pos)
+        pair.expect_commit(pos, orders)
+    assert {len(p[2]) for p in pair.pos.values()} >= set(range(7)) or heights[0] == 3
+    pair.check_from_scratch()
+    pair.close()
+
+
+def seeded_pair(rng, heights=(16, 8)):
+    pair = Pair(*heights)
+    pair.expect_commit(*pair.make_batch(rng, 12, 9, "all", (0, 2**heights[0] - 1), (0, 2**heights[1] - 1)))
+    return pair
+
+
+def test_state_batch_failures_leave_both_trees_and_say_which_item():
+    """(a) a stale previous position, (b) a stale ord_prev, (c) a new-position word >= p, (d) ord_new == p: SP_OK,
+    batch_status = SP_TREE_NOT_COMMITTED | the bit, only the offending index flagged, roots and leaves of BOTH trees
+    as before; the corrected batch then commits and equals the oracle."""
+    from starkperp import batch_np as bn
+    rng = random.Random(77)
+    pair = seeded_pair(rng)
+    felt_p = bn.felts_from_ints([P])[0]
+    for case in "abcd":
+        pos, orders = pair.make_batch(rng, 9, 7, "alternating")
+        assert any(k in pair.pos for k, _, _ in pos) and any(k in pair.ord for k, _, _ in orders)
+        arrays = list(pair.state.pack_state_batch(pos, orders))
+        want_pos, want_ord = [0] * len(pos), [0] * len(orders)
+        if case == "a":
+            j = next(i for i, (k, _, _) in enumerate(pos) if k in pair.pos)
+            stale = list(pos)
+            stale[j] = (pos[j][0], random_position(rng, 2), pos[j][2])
+            arrays = list(pair.state.pack_state_batch(stale, orders))
+            want_pos[j], bit = PREV_MISMATCH, PREV_MISMATCH
+        elif case == "b":
+            j = 3
+            arrays[6] = arrays[6].copy()
+            arrays[6][j, 0] ^= np.uint64(1)
+            want_ord[j], bit = PREV_MISMATCH, PREV_MISMATCH
+        elif case == "c":
+            j = 4  # changed (even index): its new chain exists
+            new_off = arrays[4]
+            assert new_off[j + 1] > new_off[j]
+            arrays[3] = arrays[3].copy()
+            arrays[3][int(new_off[j]) + 1] = felt_p
+            want_pos[j], bit = OUT_OF_RANGE, OUT_OF_RANGE
+        else:
+            j = len(orders) - 1
+            arrays[7] = arrays[7].copy()
+            arrays[7][j] = felt_p
+            want_ord[j], bit = OUT_OF_RANGE, OUT_OF_RANGE
+        before = pair.roots()
+        p_roots, o_roots, p_st, o_st, b_st = pair.call(arrays)
+        assert b_st == NOT_COMMITTED | bit, (case, hex(b_st))
+        assert p_st.tolist() == want_pos and o_st.tolist() == want_ord, case
+        assert p_roots == (before[0], before[0]) and o_roots == (before[1], before[1]) and pair.roots() == before
+        pair.check_leaves(random.Random(5))
+        pair.expect_commit(pos, orders)  # the corrected batch
+    # a previous chain with a word >= p is reported as that, not as a mismatch
+    pos, orders = pair.make_batch(rng, 3, 2, "none")
+    arrays = list(pair.state.pack_state_batch(pos, orders))
+    arrays[1] = arrays[1].copy()
+    arrays[1][int(arrays[2][1])] = felt_p
+    before = pair.roots()
+    _, _, p_st, o_st, b_st = pair.call(arrays)
+    assert p_st.tolist() == [0, OUT_OF_RANGE, 0] and not o_st.any() and b_st == NOT_COMMITTED | OUT_OF_RANGE
+    assert pair.roots() == before
+    pair.check_from_scratch()
+    pair.close()
+
+
+def test_state_batch_bad_arguments_write_nothing():
+    """Every SP_ERR_BAD_ARGUMENT case of the header but the two-context one (a process of its own, below): the
+    code, no output written, both roots unchanged."""
+    from starkperp import _lib
+    rng = random.Random(91)
+    pair = seeded_pair(rng)
+    lib = _lib.ensure_init()
+    pos, orders = pair.make_batch(rng, 4, 3, "all")
+    good = pair.state.pack_state_batch(pos, orders)
+    before = pair.roots()
+
+    def call(ptree, otree, arrays, n_pos=None, n_ord=None):
+        arrays = [np.ascontiguousarray(a) for a in arrays]
+        out = [np.full((1, 4), 0xA5A5, dtype=np.uint64) for _ in range(4)]
+        p_st = np.full(len(arrays[0]), 0xEE, dtype=np.uint8)
+        o_st = np.full(len(arrays[5]), 0xEE, dtype=np.uint8)
+        b_st = np.full(1, 0xEE, dtype=np.uint8)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        k, pw, po, nw, no, ok, op, on = arrays
+        rc = lib.sp_state_batch(ptree, otree, ptr(k), len(k) if n_pos is None else n_pos, ptr(pw), ptr(po), ptr(nw),
+                                ptr(no), ptr(ok), ptr(op), ptr(on), len(ok) if n_ord is None else n_ord, ptr(out[0]),
+                                ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(p_st), ptr(o_st), ptr(b_st))
+        untouched = all((o == 0xA5A5).all() for o in out) and (p_st == 0xEE).all() and (o_st == 0xEE).all() \
+            and b_st[0] == 0xEE
+        return rc, untouched
+
+    def changed(index, fn):
+        arrays = [a.copy() for a in good]
+        fn(arrays[index])
+        return arrays
+
+    def swap(a):
+        a[[1, 2]] = a[[2, 1]]
+
+    def repeat(a):
+        a[2] = a[1]
+
+    def first_one(a):
+        a[0] = 1
+
+    def dip(a):
+        a[2] = a[1] - 1
+
+    def too_big(height):
+        def fn(a):
+            a[-1] = 2**height
+        return fn
+
+    hp, ho = pair.ptree._handle, pair.otree._handle
+    cases = {
+        "position keys not increasing": (hp, ho, changed(0, swap)),
+        "position keys repeated": (hp, ho, changed(0, repeat)),
+        "order keys not increasing": (hp, ho, changed(5, swap)),
+        "position key out of range": (hp, ho, changed(0, too_big(16))),
+        "order key out of range": (hp, ho, changed(5, too_big(8))),
+        "prev_off[0] != 0": (hp, ho, changed(2, first_one)),
+        "new_off[0] != 0": (hp, ho, changed(4, first_one)),
+        "decreasing previous offset": (hp, ho, changed(2, dip)),
+        "decreasing new offset": (hp, ho, changed(4, dip)),
+        "zero-length previous chain": (hp, ho, changed(2, repeat)),
+        "unknown positions handle": (987654, ho, good),
+        "unknown orders handle": (hp, 987655, good),
+        "the same handle twice": (hp, hp, good),
+    }
+    for name, (ptree, otree, arrays) in cases.items():
+        rc, untouched = call(ptree, otree, arrays)
+        assert rc == BAD_ARGUMENT and untouched, name
+        assert pair.roots() == before, name
+    rc, untouched = call(hp, ho, good)
+    assert rc == 0 and not untouched and pair.roots() != before
+    pair.close()
+
+
+TWO_CONTEXTS = textwrap.dedent(
+    """
+    import ctypes, sys
+    sys.path.insert(0, %(root)r)
+    sys.path.insert(0, %(root)r + "/stark-perpetual_amd")
+    import numpy as np
+    from starkperp import _lib, batch_np, state
+    lib = _lib.ensure_init()
+    assert lib.sp_device_count() == 2
+    a, b, c = state.LibrarySparseTree(8, 0, 0), state.LibrarySparseTree(8, 0, 1), state.LibrarySparseTree(8, 0, 1)
+    arrays = state.pack_state_batch([(3, (0, 0, ()), (5, 6, ()))], [(9, 0, 4)])
+    arrays = (arrays[0], batch_np.felts_from_ints([0]), np.array([0, 1], dtype=np.uint32)) + arrays[3:]
+    try:
+        batch_np.state_batch(a, b, *arrays)
+        raise SystemExit("two contexts were accepted")
+    except _lib.StarkPerpError as e:
+        assert "rc=-3" in str(e) and "different contexts" in str(e), e
+    assert a.root == b.root == c.root
+    p_roots, o_roots, p_st, o_st, b_st = batch_np.state_batch(b, c, *arrays)   # both on context 1: served there
+    assert b_st == 0 and p_roots[1] == b.root != p_roots[0] and o_roots[1] == c.root != o_roots[0]
+    assert c.get(9) == 4 and a.root == p_roots[0]
+    print("two contexts ok")
+    """
+)
+
+
+def test_state_batch_refuses_trees_on_two_contexts():
+    """Needs sp_init_devices, so a process of its own (as tests/test_gpu_multi_device.py); the empty leaf 0 stands in
+    for the empty position's hash: a one-word previous chain [0]."""
+    env = dict(os.environ, STARKPERP_DEVICES="0,0", STARKPERP_WINDOW_BITS="16")
+    env.pop("LOCAL_RANK", None)
+    out = subprocess.run([sys.executable, "-c", TWO_CONTEXTS % {"root": ROOT}], capture_output=True, text=True,
+                         timeout=600, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    assert "two contexts ok" in out.stdout
+
+
+def test_state_batch_slices_above_the_ragged_launch_class():
+    """4100 changed positions = 8200 chains, above the 8192-chain launch class of the ragged kernel, plus 64 orders on
+    heights (20, 20) - against the separate-call route (position hashes, sp_tree_get, sp_tree_update: pinned by their
+    own tests) on a second pair of trees; the oracle would need tens of seconds for this one."""
+    from starkperp import batch_np, state
+    rng = random.Random(41)
+    one, two = state.SharedState(20, 20), state.SharedState(20, 20)
+    keys = sorted(rng.sample(range(2**20), 4100))
+    pos = [(k, EMPTY, random_position(rng, i % 7)) for i, k in enumerate(keys)]
+    orders = [(k, 0, rng.randrange(P)) for k in sorted(rng.sample(range(2**20), 64))]
+    p_roots, o_roots, p_st, o_st, b_st = batch_np.state_batch(one.positions, one.orders,
+                                                              *state.pack_state_batch(pos, orders))
+    assert b_st == 0 and not p_st.any() and not o_st.any()
+    assert (p_roots, o_roots) == two._apply_in_separate_calls(pos, orders)
+    assert (one.positions_root, one.orders_root) == (two.positions_root, two.orders_root) == (p_roots[1], o_roots[1])
+    probe = rng.sample(keys, 40) + [keys[0], keys[-1], keys[4095], keys[4096], rng.randrange(2**20)]
+    assert one.positions.get_many(probe) == two.positions.get_many(probe)
+    # ... and a second batch on top: every second position changes again, the others are re-stated unchanged
+    again = [(k, q, random_position(rng, 3) if i % 2 else q) for i, (k, _, q) in enumerate(pos[:600])]
+    arrays = state.pack_state_batch(again, [])
+    got = batch_np.state_batch(one.positions, one.orders, *arrays)
+    assert got[4] == 0 and (got[0], got[1]) == two._apply_in_separate_calls(again, [])
+    one.close(), two.close()
+
+
+def test_shared_state_goes_through_the_one_call_and_raises_the_same_texts(monkeypatch):
+    """SharedState with library trees: equal to the oracle twin over two batches (through sp_state_batch: the
+    separate-call route is made unreachable), and the assertion texts of the separate-call route for a stale
+    position, a stale order state and an order leaf out of range, with both roots unchanged.  An unhashable pair
+    cannot be constructed from inputs (it needs a discrete logarithm): its text is checked on the status byte the
+    library would hand back."""
+    from starkperp import batch_np, state
+    gpu = state.SharedState(64, 16)
+    gpu._apply_in_separate_calls = None
+    ref = state.SharedState(64, 16, hash_many=oracle_hash_many, position_hashes=oracle_position_hashes)
+    assert (gpu.positions_root, gpu.orders_root) == (ref.positions_root, ref.orders_root)
+    rng = random.Random(13)
+    p = [random_position(rng, n) for n in (2, 0, 5, 1)]
+    first = ([(2**64 - 1, EMPTY, p[0]), (77, EMPTY, p[1]), (76, EMPTY, p[1]), (77, p[1], p[2])],
+             [(9, 0, 10), (2**16 - 1, 0, 3), (9, 10, 25)])
+    second = ([(77, p[2], p[2]), (5, EMPTY, p[3]), (2**64 - 1, p[0], p[3])], [(9, 25, 26), (8, 0, 1)])
+    for accesses, orders in (first, second):
+        assert gpu.apply_state_updates(accesses, orders) == ref.apply_state_updates(accesses, orders)
+        assert (gpu.positions_root, gpu.orders_root) == (ref.positions_root, ref.orders_root)
+    roots = (gpu.positions_root, gpu.orders_root)
+    good_pos, good_ord = [(5, p[3], p[0])], [(8, 1, 2)]
+    for accesses, orders, text in (
+            ([(5, p[2], p[0])], good_ord, "previous position does not match the tree"),
+            ([(6, p[3], p[0])], good_ord, "previous position does not match the tree"),
+            (good_pos, [(8, 7, 2)], "previous order state does not match the tree"),
+            (good_pos, [(7, 1, 2)], "previous order state does not match the tree"),
+            (good_pos, [(8, 1, P)], "order leaf out of range")):
+        with pytest.raises(AssertionError) as err:
+            gpu.apply_state_updates(accesses, orders)
+        assert str(err.value) == text
+        assert (gpu.positions_root, gpu.orders_root) == roots
+    real = batch_np.state_batch
+
+    def unhashable(*args):
+        out = real(*args)
+        return out[:4] + (NOT_COMMITTED | 2,)
+    monkeypatch.setattr(batch_np, "state_batch", unhashable)
+    with pytest.raises(AssertionError) as err:
+        gpu.apply_state_updates([(5, p[2], p[0])], good_ord)  # (a batch that does not commit)
+    assert str(err.value) == "previous position does not match the tree"
+    monkeypatch.setattr(batch_np, "state_batch", lambda *a: ((0, 0), (0, 0), np.zeros(1, np.uint8), np.zeros(1, np.uint8),
+                                                             NOT_COMMITTED | 2))
+    with pytest.raises(AssertionError) as err:
+        gpu.apply_state_updates(good_pos, good_ord)
+    assert str(err.value) == "Unhashable input."
+    monkeypatch.setattr(batch_np, "state_batch", real)
+    assert (gpu.positions_root, gpu.orders_root) == roots
+    assert gpu.apply_state_updates(good_pos, good_ord) == ref.apply_state_updates(good_pos, good_ord)
+    gpu.close()
+
+
+def test_two_threads_name_the_same_trees_in_opposite_roles():
+    """Trees A and B of equal height and empty leaf; one thread calls (A, B), the other (B, A), 8 calls each, on
+    disjoint keys never written before - every previous value is the empty leaf whatever the interleaving.  Both
+    mutexes are taken in ascending handle order (csrc/merkle.hip sp_state_batch), so the two cannot block each
+    other; the joins are under a timeout all the same.  Final roots: the oracle's, for the union of the writes."""
+    from starkperp import batch_np as bn, state
+    height = 10
+    empty_leaf = oracle_position_hashes([EMPTY])[0]
+    a, b = state.LibrarySparseTree(height, empty_leaf), state.LibrarySparseTree(height, empty_leaf)
+    rng = random.Random(3)
+    keys = rng.sample(range(2**height), 2 * 2 * 8 * 3)
+    writes = {"a": {}, "b": {}}
+    plans = {0: [], 1: []}
+    for t in (0, 1):
+        p_name, o_name = ("a", "b") if t == 0 else ("b", "a")
+        for c in range(8):
+            mine = [keys.pop() for _ in range(6)]
+            pos = [(k, EMPTY, random_position(rng, (c + i) % 7)) for i, k in enumerate(sorted(mine[:3]))]
+            orders = [(k, empty_leaf, rng.randrange(P)) for k in sorted(mine[3:])]
+            plans[t].append(state.pack_state_batch(pos, orders))
+            writes[p_name].update(zip([k for k, _, _ in pos], oracle_position_hashes([q for _, _, q in pos])))
+            writes[o_name].update({k: v for k, _, v in orders})
+    results = {0: [], 1: []}
+
+    def run(t):
+        ptree, otree = (a, b) if t == 0 else (b, a)
+        try:
+            for arrays in plans[t]:
+                results[t].append(bn.state_batch(ptree, otree, *arrays)[2:])
+        except BaseException as e:  # noqa: BLE001 - reported by the main thread
+            results[t].append(e)
+
+    threads = [threading.Thread(target=run, args=(t,), daemon=True) for t in (0, 1)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(120)
+    assert not any(t.is_alive() for t in threads), "sp_state_batch did not return: a host deadlock"
+    for t in (0, 1):
+        assert len(results[t]) == 8
+        for got in results[t]:
+            assert not isinstance(got, BaseException), got
+            assert not got[0].any() and not got[1].any() and got[2] == 0
+    assert a.root == R.merkle_multi_update_sparse(height, writes["a"], empty_leaf, oracle_hash)
+    assert b.root == R.merkle_multi_update_sparse(height, writes["b"], empty_leaf, oracle_hash)
+    a.close(), b.close()
