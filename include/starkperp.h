@@ -376,7 +376,9 @@ int sp_public_key_batch_dev(const uint64_t* d, uint64_t* qx, uint64_t* qy, uint8
 /* Radix-2 NTT of 2^log_n felts, natural order in and out; inverse != 0 divides by n. */
 int sp_ntt_dev(const uint64_t* in, uint64_t* out, unsigned log_n, int inverse, void* stream);
 /* Coset low-degree extension of ncols columns (column c at in + c * 2^log_n felts) from <w_n> to
- * shift * <w_{n * 2^log_blowup}>, natural order; out holds ncols * 2^(log_n + log_blowup) felts. */
+ * shift * <w_{n * 2^log_blowup}>, natural order; out holds ncols * 2^(log_n + log_blowup) felts.  Any log_blowup
+ * with log_n + log_blowup <= 26 (SP_ERR_BAD_ARGUMENT above that); up to 11 the zero padding happens inside the first
+ * pass, above it the padded columns are written out first. */
 int sp_lde_dev(const uint64_t* in, uint64_t* out, unsigned ncols, unsigned log_n, unsigned log_blowup,
                const uint64_t* shift_host, void* stream);
 /* Execution trace of the Pedersen-step AIR: 512 rows per hash, columns s, px, py, lambda
@@ -466,7 +468,8 @@ int sp_fri_fold_blocks_dev(const uint64_t* fa, const uint64_t* fb, uint64_t* out
                            const uint64_t* shift_host, void* stream);
 /* The two halves of sp_lde_dev (blowup 1) as separate calls, so that the coset transforms of one column share a
  * single interpolation: evaluations on <w_n> -> coefficients in BIT-REVERSED order -> evaluations on
- * shift * <w_n> (natural order).  ncols columns 2^log_n felts apart. */
+ * shift * <w_n> (natural order).  ncols columns 2^log_n felts apart.  The intermediate array holds n times each
+ * coefficient (the 1/n is applied by sp_coset_eval_dev): it is meant for sp_coset_eval_dev alone. */
 int sp_interpolate_dev(const uint64_t* in, uint64_t* coef, unsigned ncols, unsigned log_n, void* stream);
 int sp_coset_eval_dev(const uint64_t* coef, uint64_t* out, unsigned ncols, unsigned log_n,
                       const uint64_t* shift_host, void* stream);

@@ -135,3 +135,79 @@ def verify_codes(zs, rs, ss, points):
     lib().cref_verify_batch(_pack(zs), _pack(rs), _pack(ss), _pack([p[0] for p in points]),
                             _pack([p[1] for p in points]), res, ctypes.c_size_t(n))
     return list(bytes(res))
+
+
+# ---- dense transforms over GF(p): NumPy uint64[n, 4] in and out (four little-endian words per felt) ----------
+def _felt_array(a):
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    assert a.ndim == 2 and a.shape[1] == 4, a.shape
+    return a
+
+
+def _ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _log2(n):
+    log_n = int(n).bit_length() - 1
+    assert n == 1 << log_n, "size %d is not a power of two" % n
+    return log_n
+
+
+def _felt_words(v):
+    return (ctypes.c_uint64 * 4).from_buffer_copy(int(v).to_bytes(32, "little"))
+
+
+def _ok(rc, what):
+    if rc != 0:
+        raise MemoryError("%s: out of memory in the C oracle" % what)
+
+
+def ntt_dense(col, inverse=False):
+    """stark_ref.ntt(col, root_of_unity(log_n)) / stark_ref.intt of one column, natural order on both sides."""
+    out = _felt_array(col).copy()
+    _ok(lib().cref_ntt(_ptr(out), ctypes.c_uint(_log2(out.shape[0])), ctypes.c_int(1 if inverse else 0)), "cref_ntt")
+    return out
+
+
+def lde_dense(cols, log_blowup, shift):
+    """stark_ref.lde(column, 1 << log_blowup, shift) of every column: uint64[ncols, n, 4] -> [ncols, n << log_blowup, 4]."""
+    import numpy as np
+    cols = np.ascontiguousarray(cols, dtype=np.uint64)
+    assert cols.ndim == 3 and cols.shape[2] == 4, cols.shape
+    ncols, n = cols.shape[0], cols.shape[1]
+    out = np.empty((ncols, n << log_blowup, 4), dtype=np.uint64)
+    sh = _felt_words(shift)
+    for c in range(ncols):
+        _ok(lib().cref_lde(_ptr(cols[c]), _ptr(out[c]), ctypes.c_uint(_log2(n)), ctypes.c_uint(log_blowup), sh), "cref_lde")
+    return out
+
+
+def interpolate_dense(col):
+    """What sp_interpolate_dev leaves: n times the coefficients of the interpolant over <w_n>, bit-reversed order."""
+    col = _felt_array(col)
+    out = col.copy()
+    _ok(lib().cref_interpolate(_ptr(col), _ptr(out), ctypes.c_uint(_log2(col.shape[0]))), "cref_interpolate")
+    return out
+
+
+def coset_eval_dense(coef, shift):
+    """The output of interpolate_dense -> the interpolant's values on shift * <w_n>, natural order (sp_coset_eval_dev)."""
+    coef = _felt_array(coef)
+    out = coef.copy()
+    _ok(lib().cref_coset_eval(_ptr(coef), _ptr(out), ctypes.c_uint(_log2(coef.shape[0])), _felt_words(shift)),
+        "cref_coset_eval")
+    return out
+
+
+def horner_dense(coef, points):
+    """sum_k coef[k] x^k at every x of `points` (Python ints), by Horner's rule; returns uint64[len(points), 4]."""
+    import numpy as np
+    coef = _felt_array(coef)
+    k = len(points)
+    pts = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in points), dtype="<u8").reshape(k, 4)
+    pts = np.ascontiguousarray(pts, dtype=np.uint64)
+    out = np.empty((k, 4), dtype=np.uint64)
+    lib().cref_horner(_ptr(coef), ctypes.c_size_t(coef.shape[0]), _ptr(pts), ctypes.c_size_t(k), _ptr(out))
+    return out

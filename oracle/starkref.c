@@ -10,9 +10,11 @@
  * Parity status: PINNED by tests/test_oracle_c.py against the reference-generated goldens
  * (tests/golden/g1, g2, g4, g6_c2) - the same vectors that pin oracle/ref_py.py.
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
- * The last section of the file is the OPTIMISED CPU comparator (windowed fixed-base tables + batched
+ * The section after the batch entry points is the OPTIMISED CPU comparator (windowed fixed-base tables + batched
  * affine additions): same function, a tuned algorithm, pinned by the same goldens - it exists so that
  * the GPU numbers are also compared with a CPU implementation nobody would call naive.
+ * After it comes the dense reference of the prover's transforms (NTT / coset LDE / interpolation / coset
+ * evaluation / Horner), the restatement of oracle/stark_ref.py at sizes a Python list cannot hold.
  *
  * Build: gcc -O3 -fopenmp -shared -fPIC oracle/starkref.c -o oracle/_build/libstarkref.so
  * Felts are 4 x uint64 little-endian, plain integers.
@@ -447,4 +449,176 @@ int cref_max_threads(void) {
 #else
   return 1;
 #endif
+}
+
+/* =============================================================================================
+ * Dense reference of the prover-side transforms over GF(p) (oracle/stark_ref.py ntt / intt / lde at sizes a
+ * Python list cannot hold): plain radix-2 Cooley-Tukey, a bit-reversal permutation followed by log_n
+ * decimation-in-time stages, every value canonical after every butterfly (mulmod / addmod / submod above),
+ * OpenMP over the butterflies of a stage.  Checked against stark_ref.py at small sizes and against Horner
+ * evaluation (tf_horner below: the definition) at large ones, tests/test_transform_ref_cpu.py.
+ * ============================================================================================= */
+static void tf_init(void) {
+  if (g_ready) return;
+#pragma omp critical(tf_init_tables)
+  init_tables();
+}
+/* base^e for a 256-bit exponent, square and multiply from the top bit */
+static void tf_pow(u256* r, const u256* base, const u256* e) {
+  u256 acc = {{1, 0, 0, 0}};
+  for (int i = 255; i >= 0; --i) {
+    mulmod(&acc, &acc, &acc, &MP);
+    if ((e->w[i >> 6] >> (i & 63)) & 1) mulmod(&acc, &acc, base, &MP);
+  }
+  *r = acc;
+}
+static void tf_pow_small(u256* r, const u256* base, uint64_t e) {
+  const u256 ee = {{e, 0, 0, 0}};
+  tf_pow(r, base, &ee);
+}
+/* 3^((p - 1) >> log_n): the primitive 2^log_n-th root of unity of stark_ref.root_of_unity */
+static void tf_root(u256* r, unsigned log_n) {
+  u256 e = P;
+  e.w[0] -= 1;
+  for (unsigned i = 0; i < log_n; ++i) shr1(&e, 0);
+  const u256 three = {{3, 0, 0, 0}};
+  tf_pow(r, &three, &e);
+}
+/* out[k] = base^k, k < count: blocks of 1024 consecutive powers, each started by its own exponentiation */
+static void tf_powers(u256* out, size_t count, const u256* base) {
+  const long nblk = (long)((count + 1023) / 1024);
+#pragma omp parallel for schedule(static)
+  for (long b = 0; b < nblk; ++b) {
+    const size_t lo = (size_t)b * 1024, hi = lo + 1024 < count ? lo + 1024 : count;
+    u256 cur;
+    tf_pow_small(&cur, base, (uint64_t)lo);
+    for (size_t k = lo; k < hi; ++k) { out[k] = cur; mulmod(&cur, &cur, base, &MP); }
+  }
+}
+static size_t tf_bitrev(size_t i, unsigned log_n) {
+  size_t r = 0;
+  for (unsigned b = 0; b < log_n; ++b) r |= ((i >> b) & 1) << (log_n - 1 - b);
+  return r;
+}
+static void tf_permute(u256* a, unsigned log_n) {
+  const long n = (long)1 << log_n;
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < n; ++i) {
+    const size_t r = tf_bitrev((size_t)i, log_n);
+    if ((size_t)i < r) { const u256 t = a[i]; a[i] = a[r]; a[r] = t; }
+  }
+}
+/* a[i] <- sum_k a[k] w^(i k), natural order on both sides; w a primitive 2^log_n-th root of unity.  0 on success. */
+static int tf_transform(u256* a, unsigned log_n, const u256* w) {
+  if (log_n == 0) return 0;
+  const size_t n = (size_t)1 << log_n, half = n >> 1;
+  u256* tw = (u256*)malloc(sizeof(u256) * half);
+  if (!tw) return 1;
+  tf_powers(tw, half, w);
+  tf_permute(a, log_n);
+  for (unsigned s = 1; s <= log_n; ++s) {
+    const size_t h = (size_t)1 << (s - 1);
+#pragma omp parallel for schedule(static)
+    for (long b = 0; b < (long)half; ++b) {
+      const size_t j = (size_t)b & (h - 1), i0 = (((size_t)b >> (s - 1)) << s) | j, i1 = i0 + h;
+      u256 t, lo = a[i0];
+      mulmod(&t, &a[i1], &tw[j << (log_n - s)], &MP);
+      addmod(&a[i0], &lo, &t, &P);
+      submod(&a[i1], &lo, &t, &P);
+    }
+  }
+  free(tw);
+  return 0;
+}
+static void tf_scale_all(u256* a, size_t n, const u256* f) {
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < (long)n; ++i) mulmod(&a[i], &a[i], f, &MP);
+}
+/* 1 / 2^log_n */
+static void tf_inv_n(u256* r, unsigned log_n) {
+  const u256 two = {{2, 0, 0, 0}};
+  u256 n;
+  tf_pow_small(&n, &two, log_n);
+  invmod(r, &n, &P);
+}
+
+/* In place.  inverse == 0: evaluations of sum a[k] x^k at w^i (stark_ref.ntt); otherwise the coefficients of the
+ * interpolant of a[] over <w>, 1/n included (stark_ref.intt).  0 on success, 1 out of memory. */
+int cref_ntt(uint64_t* data, unsigned log_n, int inverse) {
+  tf_init();
+  u256* a = (u256*)data;
+  u256 w;
+  tf_root(&w, log_n);
+  if (inverse) { u256 wi; invmod(&wi, &w, &P); w = wi; }
+  if (tf_transform(a, log_n, &w)) return 1;
+  if (inverse) { u256 f; tf_inv_n(&f, log_n); tf_scale_all(a, (size_t)1 << log_n, &f); }
+  return 0;
+}
+/* scratch[k] = coef[k] * shift^k for k < n, 0 for n <= k < m */
+static int tf_shift_pad(u256* out, const u256* coef, size_t n, size_t m, const u256* shift) {
+  u256* pw = (u256*)malloc(sizeof(u256) * n);
+  if (!pw) return 1;
+  tf_powers(pw, n, shift);
+#pragma omp parallel for schedule(static)
+  for (long k = 0; k < (long)n; ++k) mulmod(&out[k], &coef[k], &pw[k], &MP);
+  free(pw);
+  if (m > n) memset(out + n, 0, sizeof(u256) * (m - n));
+  return 0;
+}
+/* One column of stark_ref.lde: the interpolant of in[] over <w_n>, evaluated on shift * <w_m>, m = n << log_blowup. */
+int cref_lde(const uint64_t* in, uint64_t* out, unsigned log_n, unsigned log_blowup, const uint64_t* shift) {
+  tf_init();
+  const size_t n = (size_t)1 << log_n, m = n << log_blowup;
+  u256* coef = (u256*)malloc(sizeof(u256) * n);
+  if (!coef) return 1;
+  memcpy(coef, in, sizeof(u256) * n);
+  u256 sh;
+  memcpy(&sh, shift, 32);
+  int rc = cref_ntt((uint64_t*)coef, log_n, 1);
+  if (!rc) rc = tf_shift_pad((u256*)out, coef, n, m, &sh);
+  free(coef);
+  if (!rc) rc = cref_ntt(out, log_n + log_blowup, 0);
+  return rc;
+}
+/* include/starkperp.h sp_interpolate_dev: out[bitrev(k)] = n c_k = sum_i in[i] w^(-i k) - the coefficient WITHOUT its
+ * 1/n (sp_coset_eval_dev's table carries it), stored at the bit-reversed index. */
+int cref_interpolate(const uint64_t* in, uint64_t* out, unsigned log_n) {
+  tf_init();
+  const size_t n = (size_t)1 << log_n;
+  u256 w, wi;
+  tf_root(&w, log_n);
+  invmod(&wi, &w, &P);
+  memcpy(out, in, sizeof(u256) * n);
+  if (tf_transform((u256*)out, log_n, &wi)) return 1;
+  tf_permute((u256*)out, log_n);
+  return 0;
+}
+/* include/starkperp.h sp_coset_eval_dev: coef as cref_interpolate leaves it -> the interpolant on shift * <w_n>. */
+int cref_coset_eval(const uint64_t* coef, uint64_t* out, unsigned log_n, const uint64_t* shift) {
+  tf_init();
+  const size_t n = (size_t)1 << log_n;
+  u256* c = (u256*)malloc(sizeof(u256) * n);
+  if (!c) return 1;
+  memcpy(c, coef, sizeof(u256) * n);
+  tf_permute(c, log_n);
+  u256 f, sh;
+  tf_inv_n(&f, log_n);
+  tf_scale_all(c, n, &f);
+  memcpy(&sh, shift, 32);
+  int rc = tf_shift_pad((u256*)out, c, n, n, &sh);
+  free(c);
+  if (!rc) rc = cref_ntt(out, log_n, 0);
+  return rc;
+}
+/* out[q] = sum_k coef[k] x_q^k by Horner's rule: the definition the transforms are checked against */
+void cref_horner(const uint64_t* coef, size_t n, const uint64_t* points, size_t k, uint64_t* out) {
+  tf_init();
+  const u256* c = (const u256*)coef;
+#pragma omp parallel for schedule(dynamic, 1)
+  for (long q = 0; q < (long)k; ++q) {
+    u256 x, acc = {{0, 0, 0, 0}};
+    memcpy(&x, points + 4 * q, 32);
+    for (size_t i = n; i-- > 0;) { mulmod(&acc, &acc, &x, &MP); addmod(&acc, &acc, &c[i], &P); }
+    memcpy(out + 4 * q, &acc, 32);
+  }
 }

@@ -352,6 +352,20 @@ scale_copy_kernel(const uint64_t* __restrict__ coef, uint64_t* __restrict__ out,
   st_u256(out + 4 * j, fe_pack(fe_canon(fe_mul(ld_fe_packed(coef + 4 * j), ld_fe_packed(G + 4 * c)))));
 }
 
+// out[j << log_b] = coef[j] * G[bitrev(j)], columns 2^log_n felts apart in `coef` and 2^(log_n + log_b) in `out`: the
+// zero-padded, coset-scaled input of an LDE's big transform written out in full (the caller zeroes `out` first).  Only
+// for a blowup above the tile, which the first pass cannot pad in LDS.
+__global__ void __launch_bounds__(256)
+scale_scatter_kernel(const uint64_t* __restrict__ coef, uint64_t* __restrict__ out, int log_n, int log_b,
+                     const uint64_t* __restrict__ G) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >> log_n) return;
+  coef += ((size_t)4 << log_n) * blockIdx.y;
+  out += ((size_t)4 << (log_n + log_b)) * blockIdx.y;
+  const size_t c = log_n ? (__brevll((unsigned long long)j) >> (64 - log_n)) : 0;
+  st_u256(out + 4 * (j << log_b), fe_pack(fe_canon(fe_mul(ld_fe_packed(coef + 4 * j), ld_fe_packed(G + 4 * c)))));
+}
+
 // ---- Pedersen-step AIR --------------------------------------------------------------------------
 // Trace generation (witness): one thread per hash writes 512 rows of (s, px, py, lambda).  The
 // reference's affine chord rule (math_utils.py:59-68) costs one inversion per set bit; here the
@@ -1309,6 +1323,13 @@ int sp_lde_dev(const uint64_t* in, uint64_t* out, unsigned ncols, unsigned log_n
     if (log_blowup > 0 && (int)log_blowup <= ((int)(log_n + log_blowup) < TILE_LOG ? (int)(log_n + log_blowup) : TILE_LOG)) {
       // coset scaling + zero padding happen inside the first pass of the big transform (LDS only)
       rc = ntt_column(coef, out, (int)(log_n + log_blowup), 0, 1, 0, FE_ONE_M, st, ncols, n, m, G, (int)log_blowup);
+    } else if (log_blowup > 0) {
+      // blowup above the tile (log_n <= 14): the padding does not fit the contiguous pass, so the padded columns are
+      // written out - zeros, then coefficient j at j << log_blowup - and transformed in place
+      SP_HIP(hipMemsetAsync(out, 0, (size_t)ncols * m * 32, st));
+      hipLaunchKernelGGL(scale_scatter_kernel, dim3((unsigned)((n + 255) / 256), ncols), dim3(256), 0, st, coef, out,
+                         (int)log_n, (int)log_blowup, G);
+      rc = ntt_column(out, out, (int)(log_n + log_blowup), 0, 1, 0, FE_ONE_M, st, ncols, m, m);
     } else {  // no blowup: scale while copying, then transform in place
       hipLaunchKernelGGL(scale_copy_kernel, dim3((unsigned)((n + 255) / 256), ncols), dim3(256), 0, st, coef, out,
                          (int)log_n, G);
