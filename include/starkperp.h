@@ -191,6 +191,41 @@ int sp_tree_update(int tree, const uint64_t* keys, const uint64_t* leaves, size_
                    uint64_t* new_root, uint8_t* status);
 int sp_tree_get(int tree, const uint64_t* keys, size_t n, uint64_t* leaves);
 int sp_tree_root(int tree, uint64_t* root);
+/* Witness export.  The Cairo program takes program_input['merkle_facts'] (services/perpetual/cairo/main.cairo:39-40,
+ * 61-64): a dictionary node hash -> (left child, right child) that the two merkle_multi_update calls of
+ * state/state.cairo:155-173 walk from the previous root and from the new root, along the subtree induced by the touched
+ * leaves (starkware/python/merkle_tree.py:4-26).  The tree stores its nodes by position, so these calls read them back
+ * by position: call sp_tree_witness with the batch's squashed keys before the update and again after it, and the union
+ * of {node: (left, right)} over both results is the batch's merkle_facts for that tree.  Nothing is hashed. */
+/* Number of witness records for `keys` in a tree of `height`: sum over levels 1..height of the number of distinct
+ * keys[i] >> level.  Pure host arithmetic on the keys: callable before sp_init.  keys strictly increasing and
+ * < 2^height, 1 <= height <= 64, else SP_ERR_BAD_ARGUMENT.  n == 0 gives 0. */
+int sp_tree_witness_size(unsigned height, const uint64_t* keys, size_t n, size_t* n_records);
+/* The merkle_facts of the subtree induced by `keys` in the tree AS IT STANDS (between updates).  One record per inner
+ * node of the induced subtree, ordered by level (1 = parents of leaves ... height = the root), ascending index inside a
+ * level:
+ *   level[u], index[u]   position of the node
+ *   node[u]              its value; left[u] / right[u]: the values at (level-1, 2 index) and (level-1, 2 index + 1)
+ * A position the tree has never written reads as the empty-subtree root of its level.  *n_records always receives the
+ * count.  capacity < count: SP_ERR_BAD_ARGUMENT, nothing else written.  Host pointers, synchronous.
+ * SP_ERR_BAD_ARGUMENT with no output written at all: keys not strictly increasing, a key out of range for the tree's
+ * height, an unknown or destroyed handle.
+ * The call holds the tree's mutex from start to end, like sp_tree_get, so a witness always describes a batch boundary:
+ * never a half-committed update.  One thread per record makes three table probes (the node and its two children); a
+ * tree that has never been updated answers from the host's empty-subtree roots without a launch.
+ * Size: a record is 105 bytes (1 + 8 + 3 x 32).  4096 keys on a height-64 tree give about 2 x 10^5 records, about 23 MB
+ * back over PCIe: that copy, not the kernel, dominates the call (results up to 4 MiB go through the tree's page-locked
+ * staging buffer, larger ones are copied directly, as an update's inputs are).  Measured (tools/quick_tree_witness.py,
+ * profiles/tree_witness.txt): 0.54 ms per call, of which upload and kernels 0.09 ms, beside 1.46 ms for sp_tree_update
+ * of the same keys; sp_tree_prove of the 4096 keys 0.23 ms. */
+int sp_tree_witness(int tree, const uint64_t* keys, size_t n, size_t capacity, uint8_t* level, uint64_t* index,
+                    uint64_t* node, uint64_t* left, uint64_t* right, size_t* n_records);
+/* Inclusion proofs: leaves[i] = the leaf at keys[i] (as sp_tree_get: any order, repeats allowed) and
+ * siblings[(i*height + l)] = the value at (l, (keys[i] >> l) ^ 1), l = 0..height-1 (felts: 4 words each).  Folding
+ * leaves[i] with its siblings, H(left, right) level by level with bit l of keys[i] choosing the side, gives
+ * sp_tree_root.  A key out of range or an unknown handle: SP_ERR_BAD_ARGUMENT, nothing written.  Same locking and
+ * copy-back as sp_tree_witness; n x height (key, level) pairs must stay below 2^31. */
+int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, uint64_t* siblings);
 /* Threading of the sp_tree_* calls: a tree has its own HIP stream, work buffer and mutex.  An operation holds
  * the tree's mutex from start to end and the library lock only while it enqueues; the device work of an update
  * (the level launches) runs without the library lock, so other trees and the stateless batches go on meanwhile. */

@@ -382,6 +382,56 @@ tree_get_kernel(const TreeSlot* __restrict__ tab, uint64_t mask, const uint64_t*
 #pragma unroll
   for (int w = 0; w < 4; ++w) out[4 * (size_t)j + w] = v[w];
 }
+// ---- witness export: the tree read back by position, nothing hashed ----
+// One thread per record = per inner node of the keys' induced subtree.  idx_all is what tree_level_nodes_kernel wrote
+// (TreeLevels of the keys, level 0 = the keys): record u is node idx_all[cnt[0] + u], levels 1 .. height one after the
+// other, ascending inside a level - the order of the records.  Three probes: the node and its two children, each its
+// level's empty-subtree root (emp[level]) when the table has never seen the position.  A child may well be set where
+// the other is not and where neither is on a key's path, so neither can be derived from the other records.
+__global__ void __launch_bounds__(256)
+tree_witness_kernel(TreeLevels lv, const uint64_t* __restrict__ idx_all, const TreeSlot* __restrict__ tab, uint64_t mask,
+                    const uint64_t* __restrict__ emp, uint64_t* __restrict__ node, uint64_t* __restrict__ left,
+                    uint64_t* __restrict__ right, unsigned n_records) {
+  const unsigned u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= n_records) return;
+  const unsigned g = lv.cnt[0] + u;  // position in idx_all; idx_off is the running node count
+  unsigned level = 1;
+  while (level < lv.height && g >= lv.idx_off[level + 1]) ++level;
+  const uint64_t index = idx_all[g];  // < 2^(64 - level): 2 index + 1 cannot wrap
+  const uint64_t* v = tree_find(tab, mask, level, index);
+  const uint64_t* l = tree_find(tab, mask, level - 1, 2 * index);
+  const uint64_t* r = tree_find(tab, mask, level - 1, 2 * index + 1);
+  if (!v) v = emp + 4 * level;
+  if (!l) l = emp + 4 * (level - 1);
+  if (!r) r = emp + 4 * (level - 1);
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    node[4 * (size_t)u + w] = v[w];
+    left[4 * (size_t)u + w] = l[w];
+    right[4 * (size_t)u + w] = r[w];
+  }
+}
+// One thread per (key, level): siblings[key j][level] = the node beside the path of keys[j] at `level` (0 .. height - 1,
+// so the shift is below 64 and the sibling's index at level 63 is 0 or 1); the level-0 thread also writes the leaf.
+__global__ void __launch_bounds__(256)
+tree_prove_kernel(const TreeSlot* __restrict__ tab, uint64_t mask, const uint64_t* __restrict__ keys, unsigned height,
+                  const uint64_t* __restrict__ emp, uint64_t* __restrict__ leaves, uint64_t* __restrict__ siblings,
+                  unsigned n_pairs) {
+  const unsigned g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_pairs) return;
+  const unsigned j = g / height, level = g - j * height;
+  const uint64_t key = keys[j];
+  const uint64_t* s = tree_find(tab, mask, level, (key >> level) ^ 1ull);
+  if (!s) s = emp + 4 * level;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) siblings[4 * (size_t)g + w] = s[w];
+  if (level == 0) {
+    const uint64_t* v = tree_find(tab, mask, 0, key);
+    if (!v) v = emp;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) leaves[4 * (size_t)j + w] = v[w];
+  }
+}
 // ---- the leaf kernels of sp_state_batch: one thread per item, in front of the update's structure kernels ----
 // Status bits raised by any lane go into the stream's status flag with one atomic per wave.
 __device__ __forceinline__ void tree_raise(unsigned* __restrict__ flag, unsigned bits) {
@@ -636,36 +686,30 @@ static bool tree_keys_ok(const SparseTree& t, const uint64_t* keys, size_t n) {
   return true;
 }
 
-// `enqueued`, when given, is called once the levels are on the stream and the library lock is free again.
-static int tree_enqueue(SparseTree& t, const uint64_t* keys, const uint64_t* leaves, size_t n, uint64_t* old_root,
-                        uint8_t* status, const LeafProducer* producer, TreePending& p,
-                        const std::function<void()>* enqueued = nullptr) {
-  const unsigned height = t.height;
-  if (!tree_keys_ok(t, keys, n)) return SP_ERR_BAD_ARGUMENT;
-  int rc = tree_root_locked(t, old_root);
-  if (rc != SP_OK) return rc;
-  if (status) *status = 0;
-  p.queued = false;
-  if (n == 0) return SP_OK;
-  // ---- host: only the node COUNT of every level (merkle_tree.py:18-26 on the keys alone): level l has one node
-  // per distinct key >> l, i.e. 1 + the adjacent key pairs whose highest differing bit is >= l ----
-  std::vector<size_t> cnt(height + 1);
-  {
-    size_t hist[65] = {0};
-    for (size_t i = 1; i < n; ++i) ++hist[63 - __builtin_clzll(keys[i] ^ keys[i - 1])];
-    size_t above = 0;
-    for (int l = 64; l >= 0; --l) {
-      if (l < 64) above += hist[l];
-      if ((unsigned)l <= height) cnt[l] = 1 + above;
-    }
+// ---- host: only the node COUNT of every level (merkle_tree.py:18-26 on the keys alone): level l has one node
+// per distinct key >> l, i.e. 1 + the adjacent key pairs whose highest differing bit is >= l.  keys sorted, n >= 1;
+// cnt[0 .. height].  Shared by an update (tree_enqueue) and a witness (sp_tree_witness_size, sp_tree_witness). ----
+static void tree_level_counts(unsigned height, const uint64_t* keys, size_t n, std::vector<size_t>& cnt) {
+  cnt.assign(height + 1, 0);
+  size_t hist[65] = {0};
+  for (size_t i = 1; i < n; ++i) ++hist[63 - __builtin_clzll(keys[i] ^ keys[i - 1])];
+  size_t above = 0;
+  for (int l = 64; l >= 0; --l) {
+    if (l < 64) above += hist[l];
+    if ((unsigned)l <= height) cnt[l] = 1 + above;
   }
-  size_t total = 0;
+}
+// The TreeLevels of the keys' induced subtree and the sizes of its arrays: `total` nodes over all levels, `felts`
+// values, `idxs` node indices, `srcs` child lists.  false: too large for the 32-bit positions of the kernels.
+static bool tree_layout(unsigned height, const uint64_t* keys, size_t n, std::vector<size_t>& cnt, TreeLevels& lv,
+                        size_t& total, size_t& felts, size_t& idxs, size_t& srcs) {
+  tree_level_counts(height, keys, n, cnt);
+  total = 0;
   for (unsigned l = 0; l <= height; ++l) total += cnt[l];
   // felts: [level 0 values][siblings for level 1's parents][level 1 values][siblings ...] ...
-  TreeLevels& lv = p.lv;
   std::memset(&lv, 0, sizeof(lv));
   lv.height = height;
-  size_t felts = 0, idxs = 0, srcs = 0;
+  felts = idxs = srcs = 0;
   for (unsigned l = 0; l <= height; ++l) {
     lv.cnt[l] = (unsigned)cnt[l];
     lv.val_base[l] = (int)felts;
@@ -679,7 +723,24 @@ static int tree_enqueue(SparseTree& t, const uint64_t* keys, const uint64_t* lea
       srcs += cnt[l + 1];
     }
   }
-  if (felts >= (size_t)INT_MAX || total > 0x7fffffffull) { set_error("update too large"); return SP_ERR_BAD_ARGUMENT; }
+  return felts < (size_t)INT_MAX && total <= 0x7fffffffull;
+}
+
+// `enqueued`, when given, is called once the levels are on the stream and the library lock is free again.
+static int tree_enqueue(SparseTree& t, const uint64_t* keys, const uint64_t* leaves, size_t n, uint64_t* old_root,
+                        uint8_t* status, const LeafProducer* producer, TreePending& p,
+                        const std::function<void()>* enqueued = nullptr) {
+  const unsigned height = t.height;
+  if (!tree_keys_ok(t, keys, n)) return SP_ERR_BAD_ARGUMENT;
+  int rc = tree_root_locked(t, old_root);
+  if (rc != SP_OK) return rc;
+  if (status) *status = 0;
+  p.queued = false;
+  if (n == 0) return SP_OK;
+  std::vector<size_t> cnt;
+  TreeLevels& lv = p.lv;
+  size_t total = 0, felts = 0, idxs = 0, srcs = 0;
+  if (!tree_layout(height, keys, n, cnt, lv, total, felts, idxs, srcs)) { set_error("update too large"); return SP_ERR_BAD_ARGUMENT; }
   tl_mark("tree: level counts");
   rc = tree_reserve(t, total);
   if (rc != SP_OK) return rc;
@@ -943,6 +1004,206 @@ int sp_tree_get(int tree, const uint64_t* keys, size_t n, uint64_t* leaves) {
   SP_HIP(hipGetLastError());
   SP_HIP(hipMemcpyAsync(leaves, d_out, n * 32, hipMemcpyDeviceToHost, t.stream));
   SP_HIP(hipStreamSynchronize(t.stream));
+  return SP_OK;
+}
+
+// ---- witness export (include/starkperp.h): the preimages that main.cairo:39-40,61-64 takes as merkle_facts and that
+// the merkle_multi_update calls of state/state.cairo:155-173 walk (merkle_tree.py:4-26), read back by position ----
+int sp_tree_witness_size(unsigned height, const uint64_t* keys, size_t n, size_t* n_records) {
+  if (!n_records || (n && !keys)) { set_error("sp_tree_witness_size: null argument"); return SP_ERR_BAD_ARGUMENT; }
+  if (height < 1 || height > 64) { set_error("height must be in 1..64"); return SP_ERR_BAD_ARGUMENT; }
+  for (size_t i = 0; i < n; ++i) {
+    if (i > 0 && keys[i] <= keys[i - 1]) { set_error("keys must be strictly increasing"); return SP_ERR_BAD_ARGUMENT; }
+    if (height < 64 && (keys[i] >> height) != 0) { set_error("key out of range for height"); return SP_ERR_BAD_ARGUMENT; }
+  }
+  size_t records = 0;
+  if (n) {
+    std::vector<size_t> cnt;
+    tree_level_counts(height, keys, n, cnt);
+    for (unsigned l = 1; l <= height; ++l) records += cnt[l];
+  }
+  *n_records = records;
+  return SP_OK;
+}
+
+// The empty-subtree roots of the tree's levels, a copy (tree mutex held; the cache and the scratch map are shared).
+static int tree_empty_roots(const SparseTree& t, std::vector<uint64_t>& out) {
+  ctx_lock lk(global_mu());
+  Scratch s;
+  int rc = get_scratch_public(1, s, 0);
+  if (rc != SP_OK) return rc;
+  const std::vector<uint64_t>* emp = nullptr;
+  rc = empty_roots(t.empty_leaf, s, &emp);
+  if (rc != SP_OK) return rc;
+  out.assign(emp->begin(), emp->begin() + 4 * ((size_t)t.height + 1));
+  return SP_OK;
+}
+
+int sp_tree_witness(int tree, const uint64_t* keys, size_t n, size_t capacity, uint8_t* level, uint64_t* index,
+                    uint64_t* node, uint64_t* left, uint64_t* right, size_t* n_records) {
+  SP_REQUIRE_READY();
+  if (!n_records || (n && !keys)) { set_error("sp_tree_witness: null argument"); return SP_ERR_BAD_ARGUMENT; }
+  TimelineScope timeline("sp_tree_witness");
+  TreeScope ts;
+  int rc = ts.open(tree);
+  if (rc != SP_OK) return rc;
+  SparseTree& t = *ts.t;
+  const unsigned height = t.height;
+  if (!tree_keys_ok(t, keys, n)) return SP_ERR_BAD_ARGUMENT;
+  if (n == 0) { *n_records = 0; return SP_OK; }
+  std::vector<size_t> cnt;
+  TreeLevels lv;
+  size_t total = 0, felts = 0, idxs = 0, srcs = 0;
+  if (!tree_layout(height, keys, n, cnt, lv, total, felts, idxs, srcs)) { set_error("witness too large"); return SP_ERR_BAD_ARGUMENT; }
+  const size_t records = total - n;  // every node above level 0
+  *n_records = records;
+  if (capacity < records) { set_error("sp_tree_witness: capacity below the record count"); return SP_ERR_BAD_ARGUMENT; }
+  if (!level || !index || !node || !left || !right) { set_error("sp_tree_witness: null output array"); return SP_ERR_BAD_ARGUMENT; }
+  std::vector<uint64_t> emp;
+  rc = tree_empty_roots(t, emp);
+  if (rc != SP_OK) return rc;
+  if (!t.table) {  // never updated: every position is its level's empty-subtree root; the indices as the kernel finds them
+    size_t u = 0;
+    for (unsigned l = 1; l <= height; ++l) {
+      for (size_t i = 0; i < n; ++i) {
+        const uint64_t me = l < 64 ? keys[i] >> l : 0;
+        if (i > 0 && (l < 64 ? keys[i - 1] >> l : 0) == me) continue;
+        level[u] = (uint8_t)l;
+        index[u] = me;
+        std::memcpy(node + 4 * u, &emp[4 * l], 32);
+        std::memcpy(left + 4 * u, &emp[4 * (l - 1)], 32);
+        std::memcpy(right + 4 * u, &emp[4 * (l - 1)], 32);
+        ++u;
+      }
+    }
+    return SP_OK;
+  }
+  // work buffer: empty roots | node indices of levels 0 .. height (level 0 = the keys) | node | left | right values.
+  // What goes back - the indices of levels 1 .. height and the three value arrays - is one contiguous piece.
+  const size_t emp_bytes = ((size_t)height + 1) * 32, in_bytes = emp_bytes + n * 8, out_bytes = records * (8 + 96);
+  SP_HIP(t.buf.reserve(in_bytes + out_bytes + 64));
+  char* b = (char*)t.buf.ptr;
+  uint64_t* d_emp = (uint64_t*)b;
+  uint64_t* d_idx = (uint64_t*)(b + emp_bytes);
+  uint64_t* d_node = d_idx + total;
+  uint64_t* d_left = d_node + 4 * records;
+  uint64_t* d_right = d_left + 4 * records;
+  hipStream_t st = t.stream;
+  tl_mark("witness: work buffer ready");
+  // small results through the tree's page-locked buffer (its previous user has finished: every operation ends with a
+  // wait on the stream), larger ones directly into the caller's arrays
+  char* stage = nullptr;
+  if (in_bytes + out_bytes <= PINNED_STAGE_MAX && t.hbuf.reserve(in_bytes + out_bytes) == hipSuccess) stage = (char*)t.hbuf.ptr;
+  else (void)hipGetLastError();
+  if (stage) {
+    std::memcpy(stage, emp.data(), emp_bytes);
+    std::memcpy(stage + emp_bytes, keys, n * 8);
+    SP_HIP(hipMemcpyAsync(d_emp, stage, in_bytes, hipMemcpyHostToDevice, st));
+  } else {
+    SP_HIP(hipMemcpyAsync(d_emp, emp.data(), emp_bytes, hipMemcpyHostToDevice, st));
+    SP_HIP(hipMemcpyAsync(d_idx, keys, n * 8, hipMemcpyHostToDevice, st));
+  }
+  hipLaunchKernelGGL(tree_level_nodes_kernel, dim3(height), dim3(1024), 0, st, lv, d_idx, d_idx);
+  hipLaunchKernelGGL(tree_witness_kernel, dim3((unsigned)((records + 255) / 256)), dim3(256), 0, st, lv, d_idx, t.table,
+                     t.slots - 1, d_emp, d_node, d_left, d_right, (unsigned)records);
+  SP_HIP(hipGetLastError());
+  tl_mark("witness: kernels enqueued");
+  if (timeline.mine) {  // diagnostics only (STARKPERP_TIMELINE=1): an extra wait that tells the kernels from the copy back
+    SP_HIP(hipStreamSynchronize(st));
+    tl_mark("witness: kernels done");
+  }
+  if (stage) {
+    SP_HIP(hipMemcpyAsync(stage + in_bytes, d_idx + n, out_bytes, hipMemcpyDeviceToHost, st));
+  } else {
+    SP_HIP(hipMemcpyAsync(index, d_idx + n, records * 8, hipMemcpyDeviceToHost, st));
+    SP_HIP(hipMemcpyAsync(node, d_node, records * 32, hipMemcpyDeviceToHost, st));
+    SP_HIP(hipMemcpyAsync(left, d_left, records * 32, hipMemcpyDeviceToHost, st));
+    SP_HIP(hipMemcpyAsync(right, d_right, records * 32, hipMemcpyDeviceToHost, st));
+  }
+  SP_HIP(hipStreamSynchronize(st));
+  tl_mark("witness: results on the host");
+  if (stage) {
+    const char* o = stage + in_bytes;
+    std::memcpy(index, o, records * 8);
+    std::memcpy(node, o + records * 8, records * 32);
+    std::memcpy(left, o + records * 40, records * 32);
+    std::memcpy(right, o + records * 72, records * 32);
+  }
+  // the level of a record is a function of the level counts alone: filled here, it does not cross PCIe
+  size_t u = 0;
+  for (unsigned l = 1; l <= height; ++l) {
+    std::memset(level + u, (int)l, cnt[l]);
+    u += cnt[l];
+  }
+  return SP_OK;
+}
+
+int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, uint64_t* siblings) {
+  SP_REQUIRE_READY();
+  if (n && (!keys || !leaves || !siblings)) { set_error("sp_tree_prove: null argument"); return SP_ERR_BAD_ARGUMENT; }
+  TimelineScope timeline("sp_tree_prove");
+  TreeScope ts;
+  int rc = ts.open(tree);
+  if (rc != SP_OK) return rc;
+  SparseTree& t = *ts.t;
+  const unsigned height = t.height;
+  for (size_t i = 0; i < n; ++i) {
+    if (height < 64 && (keys[i] >> height) != 0) { set_error("key out of range for height"); return SP_ERR_BAD_ARGUMENT; }
+  }
+  if (n == 0) return SP_OK;
+  if (n > 0x7fffffffull / height) { set_error("too many keys"); return SP_ERR_BAD_ARGUMENT; }
+  const size_t pairs = n * height;
+  std::vector<uint64_t> emp;
+  rc = tree_empty_roots(t, emp);
+  if (rc != SP_OK) return rc;
+  if (!t.table) {  // never updated: the empty leaf under a path of empty-subtree roots
+    for (size_t i = 0; i < n; ++i) {
+      std::memcpy(leaves + 4 * i, emp.data(), 32);
+      std::memcpy(siblings + 4 * i * height, emp.data(), (size_t)height * 32);
+    }
+    return SP_OK;
+  }
+  // work buffer: empty roots | keys | leaves | siblings; leaves and siblings go back as one piece
+  const size_t emp_bytes = ((size_t)height + 1) * 32, in_bytes = emp_bytes + n * 8, out_bytes = (n + pairs) * 32;
+  SP_HIP(t.buf.reserve(in_bytes + out_bytes + 64));
+  char* b = (char*)t.buf.ptr;
+  uint64_t* d_emp = (uint64_t*)b;
+  uint64_t* d_keys = (uint64_t*)(b + emp_bytes);
+  uint64_t* d_leaves = d_keys + n;
+  uint64_t* d_sib = d_leaves + 4 * n;
+  hipStream_t st = t.stream;
+  tl_mark("prove: work buffer ready");
+  char* stage = nullptr;
+  if (in_bytes + out_bytes <= PINNED_STAGE_MAX && t.hbuf.reserve(in_bytes + out_bytes) == hipSuccess) stage = (char*)t.hbuf.ptr;
+  else (void)hipGetLastError();
+  if (stage) {
+    std::memcpy(stage, emp.data(), emp_bytes);
+    std::memcpy(stage + emp_bytes, keys, n * 8);
+    SP_HIP(hipMemcpyAsync(d_emp, stage, in_bytes, hipMemcpyHostToDevice, st));
+  } else {
+    SP_HIP(hipMemcpyAsync(d_emp, emp.data(), emp_bytes, hipMemcpyHostToDevice, st));
+    SP_HIP(hipMemcpyAsync(d_keys, keys, n * 8, hipMemcpyHostToDevice, st));
+  }
+  hipLaunchKernelGGL(tree_prove_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, t.table, t.slots - 1,
+                     d_keys, height, d_emp, d_leaves, d_sib, (unsigned)pairs);
+  SP_HIP(hipGetLastError());
+  tl_mark("prove: kernel enqueued");
+  if (timeline.mine) {  // diagnostics only, as in sp_tree_witness
+    SP_HIP(hipStreamSynchronize(st));
+    tl_mark("prove: kernel done");
+  }
+  if (stage) {
+    SP_HIP(hipMemcpyAsync(stage + in_bytes, d_leaves, out_bytes, hipMemcpyDeviceToHost, st));
+  } else {
+    SP_HIP(hipMemcpyAsync(leaves, d_leaves, n * 32, hipMemcpyDeviceToHost, st));
+    SP_HIP(hipMemcpyAsync(siblings, d_sib, pairs * 32, hipMemcpyDeviceToHost, st));
+  }
+  SP_HIP(hipStreamSynchronize(st));
+  tl_mark("prove: results on the host");
+  if (stage) {
+    std::memcpy(leaves, stage + in_bytes, n * 32);
+    std::memcpy(siblings, stage + in_bytes + n * 32, pairs * 32);
+  }
   return SP_OK;
 }
 

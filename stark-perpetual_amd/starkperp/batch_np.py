@@ -261,3 +261,44 @@ def state_batch(positions_tree, orders_tree, pos_keys, prev_words, prev_off, new
         "sp_state_batch")
     r = ints_from_felts(roots)
     return (r[0], r[1]), (r[2], r[3]), pos_st, ord_st, int(batch_st[0])
+
+
+def tree_witness_size(height, keys) -> int:
+    """Number of records sp_tree_witness returns for `keys` (uint64[n], strictly increasing) in a tree of `height`:
+    host arithmetic inside the library, no GPU and no sp_init needed."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    assert keys.ndim == 1
+    count = ctypes.c_size_t()
+    _lib.check(_lib.load().sp_tree_witness_size(height, _ptr(keys), keys.shape[0], ctypes.byref(count)),
+               "sp_tree_witness_size")
+    return count.value
+
+
+def tree_witness(tree, keys):
+    """The merkle_facts (main.cairo:39-40, 61-64) of the subtree induced by `keys` (uint64[n], strictly increasing) in
+    `tree` (a state.LibrarySparseTree) as it stands: one record per inner node, level 1 (parents of leaves) up to the
+    root, ascending index inside a level.  Returns (level uint8[R], index uint64[R], node, left, right uint64[R, 4])."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    assert keys.ndim == 1
+    n = keys.shape[0]
+    cap = tree_witness_size(tree.height, keys)
+    level, index = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint64)
+    node, left, right = (np.zeros((cap, 4), dtype=np.uint64) for _ in range(3))
+    count = ctypes.c_size_t()
+    _lib.check(_lib.ensure_init().sp_tree_witness(tree._handle, _ptr(keys), n, cap, _ptr(level), _ptr(index), _ptr(node),
+                                                  _ptr(left), _ptr(right), ctypes.byref(count)), "sp_tree_witness")
+    assert count.value == cap
+    return level, index, node, left, right
+
+
+def tree_prove(tree, keys):
+    """Inclusion proofs of `keys` (uint64[n], any order, repeats allowed) in `tree` (a state.LibrarySparseTree): returns
+    (leaves uint64[n, 4], siblings uint64[n, height, 4]); siblings[i, l] sits at level l beside the path of keys[i]."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    assert keys.ndim == 1
+    n, height = keys.shape[0], tree.height
+    leaves = np.zeros((n, 4), dtype=np.uint64)
+    siblings = np.zeros((n, height, 4), dtype=np.uint64)
+    _lib.check(_lib.ensure_init().sp_tree_prove(tree._handle, _ptr(keys), n, _ptr(leaves), _ptr(siblings)),
+               "sp_tree_prove")
+    return leaves, siblings

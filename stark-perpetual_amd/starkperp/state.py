@@ -134,12 +134,62 @@ class SparseMerkleTree:
         self.root = layer[0]
         return old_root, self.root
 
+    def witness(self, keys: Iterable[int]) -> List[Tuple[int, int, int, int, int]]:
+        """The merkle_facts of the subtree induced by `keys` (sorted and made distinct first) in the tree as it stands:
+        one (level, index, node, left, right) per inner node, level 1 (parents of leaves) up to the root, ascending
+        index inside a level - what merkle_multi_update walks from this root (merkle_tree.py:4-26).  Read from the
+        facts store by walking down from the root."""
+        keys = sorted(set(keys))
+        for k in keys:
+            assert 0 <= k < (1 << self.height), "key out of range for height"
+        if not keys:
+            return []
+        levels: List[List[Tuple[int, int, int, int, int]]] = [[] for _ in range(self.height + 1)]
+        values = {0: self.root}
+        for level in range(self.height, 0, -1):
+            below = {}
+            for idx in sorted(set(k >> level for k in keys)):
+                left, right = self._children(values[idx], level)
+                levels[level].append((level, idx, values[idx], left, right))
+                below[2 * idx], below[2 * idx + 1] = left, right
+            values = below
+        return [rec for level in levels for rec in level]
+
+    def prove(self, keys: Sequence[int]) -> List[Tuple[int, List[int]]]:
+        """Inclusion proofs: per key (any order, repeats allowed) the leaf and its sibling path, siblings[l] at level l
+        (0 = the leaf's own sibling ... height - 1 = the other child of the root)."""
+        out = []
+        for key in keys:
+            assert 0 <= key < (1 << self.height), "key out of range for height"
+            node, siblings = self.root, [0] * self.height
+            for level in range(self.height, 0, -1):
+                left, right = self._children(node, level)
+                bit = (key >> (level - 1)) & 1
+                node, siblings[level - 1] = (right, left) if bit else (left, right)
+            out.append((node, siblings))
+        return out
+
+
+def facts_of(witness) -> Dict[int, Tuple[int, int]]:
+    """Witness records -> {node: (left, right)}: the shape of program_input['merkle_facts'] (main.cairo:39-40)."""
+    return {node: (left, right) for _, _, node, left, right in witness}
+
+
+def proof_root(key: int, leaf: int, siblings: Sequence[int], hash_many) -> int:
+    """Folds an inclusion proof (SparseMerkleTree.prove / LibrarySparseTree.prove) to the root it commits to."""
+    node = leaf
+    for level, sib in enumerate(siblings):
+        left, right = (sib, node) if (key >> level) & 1 else (node, sib)
+        node = hash_many([left], [right])[0]
+    return node
+
 
 class LibrarySparseTree:
     """The same tree with its state kept by the library (sp_tree_*, csrc/merkle.hip): one call per
     update instead of one host round trip per level - 4096 leaves at height 64 in about 15 ms
-    instead of 270.  Same interface as SparseMerkleTree (`update`, `get`, `root`); node preimages
-    are not exposed (the library stores nodes by position, not by hash)."""
+    instead of 270.  Same interface as SparseMerkleTree (`update`, `get`, `root`, `witness`, `prove`): the library
+    stores nodes by position, not by hash, and `witness` reads the preimages of an induced subtree back by position
+    (sp_tree_witness)."""
 
     def __init__(self, height: int, empty_leaf: int = 0, context: int = 0):
         """context: which device of sp_init_devices keeps the tree (0 = the primary; one process per GPU has only that)."""
@@ -202,6 +252,32 @@ class LibrarySparseTree:
         if st[0]:
             raise AssertionError("Unhashable input." if st[0] & 2 else "leaf out of range")
         return self._lib.unpack_felts(old, 1)[0], self._lib.unpack_felts(new, 1)[0]
+
+    def witness(self, keys: Iterable[int]) -> List[Tuple[int, int, int, int, int]]:
+        """As SparseMerkleTree.witness, read from the library's node table in one call (sp_tree_witness)."""
+        import numpy as np
+        from . import batch_np
+        keys = sorted(set(keys))
+        for k in keys:
+            assert 0 <= k < (1 << self.height), "key out of range for height"
+        if not keys:
+            return []
+        level, index, node, left, right = batch_np.tree_witness(self, np.array(keys, dtype=np.uint64))
+        return list(zip(level.tolist(), index.tolist(), batch_np.ints_from_felts(node), batch_np.ints_from_felts(left),
+                        batch_np.ints_from_felts(right)))
+
+    def prove(self, keys: Sequence[int]) -> List[Tuple[int, List[int]]]:
+        """As SparseMerkleTree.prove, in one call (sp_tree_prove)."""
+        import numpy as np
+        from . import batch_np
+        keys = list(keys)
+        for k in keys:
+            assert 0 <= k < (1 << self.height), "key out of range for height"
+        if not keys:
+            return []
+        leaves, siblings = batch_np.tree_prove(self, np.array(keys, dtype=np.uint64))
+        leaves, flat, h = batch_np.ints_from_felts(leaves), batch_np.ints_from_felts(siblings), self.height
+        return [(leaf, flat[i * h:(i + 1) * h]) for i, leaf in enumerate(leaves)]
 
     def close(self):
         if self._handle is not None:
@@ -296,16 +372,32 @@ class SharedState:
     def orders_root(self) -> int:
         return self.orders.root
 
-    def apply_state_updates(self, position_accesses, order_accesses):
+    def apply_state_updates(self, position_accesses, order_accesses, facts=None):
         """shared_state_apply_state_updates (state/state.cairo:135-186): squash, hash the previous
         and new positions (hash_position_updates), check the previous leaves against the tree,
         merkle-multi-update both trees.  Returns ((old_pos_root, new_pos_root), (old_ord, new_ord)).
         When the library keeps both trees and hashes the positions, all of it is ONE library call (sp_state_batch,
-        _apply_in_one_call); with an injected hash the steps are separate calls (_apply_in_separate_calls)."""
+        _apply_in_one_call); with an injected hash the steps are separate calls (_apply_in_separate_calls).
+        facts: a dict that receives the batch's merkle_facts (main.cairo:39-40, 61-64) for both trees - the witness
+        of the squashed keys before the update and again after it, {node: (left, right)} - merged in only when the
+        batch commits: a batch that raises leaves the dict as it was.  None: nothing is read back."""
         if (isinstance(self.positions, LibrarySparseTree) and isinstance(self.orders, LibrarySparseTree)
                 and self._position_hashes is position_hashes_many):
-            return self._apply_in_one_call(position_accesses, order_accesses)
-        return self._apply_in_separate_calls(position_accesses, order_accesses)
+            apply = self._apply_in_one_call
+        else:
+            apply = self._apply_in_separate_calls
+        if facts is None:
+            return apply(position_accesses, order_accesses)
+        touched = [(self.positions, [key for key, _, _ in squash_updates(position_accesses)]),
+                   (self.orders, [key for key, _, _ in squash_updates(order_accesses)])]
+        collected: Dict[int, Tuple[int, int]] = {}
+        for tree, keys in touched:
+            collected.update(facts_of(tree.witness(keys)))
+        roots = apply(position_accesses, order_accesses)
+        for tree, keys in touched:
+            collected.update(facts_of(tree.witness(keys)))
+        facts.update(collected)
+        return roots
 
     def _apply_in_one_call(self, position_accesses, order_accesses):
         """Through sp_state_batch: the previous-leaf checks, both trees' hashing and the all-or-nothing decision
