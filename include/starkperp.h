@@ -23,7 +23,7 @@
  *     serialises the host-side bookkeeping; scratch, window tables of the verifier and NTT work
  *     columns are per stream, so _dev calls on different streams overlap on the device.  The
  *     host-pointer batches that carry no shared state - sp_pedersen_batch, sp_pedersen_chains,
- *     sp_pedersen_chains_ragged,
+ *     sp_pedersen_chains_ragged, sp_merkle_fold_paths, sp_merkle_verify_paths,
  *     sp_ecdsa_verify_batch (per-signature ladder), sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch,
  *     sp_public_key_batch -
  *     run on one of 16 host lanes (own stream, own staging buffer) and hold the lock only while a
@@ -93,7 +93,7 @@ int sp_init(int device, int window_bits);
  *     sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch, sp_public_key_batch take the context of the host lane
  *     they are handed (lanes go round-robin over the contexts, so concurrent host threads spread over the
  *     devices), and one call of sp_pedersen_batch / sp_ecdsa_verify_batch with 16384 items or more is cut into
- *     one contiguous slice per context, the slices running side by side on host threads of the library; sp_pedersen_batch_dev, sp_pedersen_chains_dev, sp_pedersen_chains_ragged_dev, sp_merkle_build_dev, sp_merkle_forest_dev,
+ *     one contiguous slice per context, the slices running side by side on host threads of the library; sp_pedersen_batch_dev, sp_pedersen_chains_dev, sp_pedersen_chains_ragged_dev, sp_merkle_fold_paths_dev, sp_merkle_build_dev, sp_merkle_forest_dev,
  *     sp_commit_rows_dev, sp_ecdsa_verify_batch_dev, sp_ecdsa_sign_batch_dev, sp_ecdsa_sign_rfc6979_batch_dev and
  *     sp_public_key_batch_dev run on the device their pointers live on (the stream
  *     must belong to that device);
@@ -226,6 +226,36 @@ int sp_tree_witness(int tree, const uint64_t* keys, size_t n, size_t capacity, u
  * sp_tree_root.  A key out of range or an unknown handle: SP_ERR_BAD_ARGUMENT, nothing written.  Same locking and
  * copy-back as sp_tree_witness; n x height (key, level) pairs must stay below 2^31. */
 int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, uint64_t* siblings);
+/* Verifying inclusion proofs: Merkle paths folded on the device, all of a call in ONE launch (ped_path_fold_kernel)
+ * that lasts as long as its longest path.  node = pedersen_hash(left, right) (signature.py:296-318); bit l of keys[i]
+ * says whether the running node is the RIGHT child at level l (starkware/python/merkle_tree.py:4-26,
+ * state/state.cairo:155-173): h <- H(sibling, h) if it is set, h <- H(h, sibling) if not, starting from h = leaves[i].
+ *   off == NULL   every path has `height` siblings, sibling l of item i at siblings + 4 (i height + l): exactly the
+ *                 layout sp_tree_prove writes, so its output is this call's input
+ *   off != NULL   n + 1 HOST offsets in felts, off[0] = 0, non-decreasing; path i has off[i+1] - off[i] siblings
+ *                 (0 .. 64) from siblings + 4 off[i]; `height` is ignored.  A path of no siblings folds to its leaf.
+ *   keys          n HOST words in all three calls, like `off`; every bit at or above the path's length must be 0
+ *   roots[i]      the folded root (n felts); status[i] (n bytes or NULL) = OR of the SP_HASH_* bytes of path i's
+ *                 hashes: SP_HASH_OUT_OF_RANGE if the leaf (also of a path of no siblings) or a sibling is >= p
+ *   expected      n_expected = 1 (one root for all paths) or n roots; verdict[i] = SP_PATH_TRUE only if status[i] is 0
+ *                 and the folded root equals the expected one
+ * SP_ERR_BAD_ARGUMENT, with nothing written: off[0] != 0, a decreasing offset, a path longer than 64, height > 64
+ * while off is NULL, a key bit set at or above its path's length, n_expected outside {1, n}, more than 2^32 - 1
+ * sibling felts.  n == 0 is SP_OK.
+ * The _dev call takes leaves, siblings, roots and status on the device, enqueues and returns; it has copied `off`
+ * and `keys` by then.  The host calls run on a host lane of the primary context (as sp_pedersen_chains_ragged);
+ * sp_merkle_verify_paths compares on the device: only the n verdict bytes (and n status bytes when asked for) come
+ * back over PCIe.  Batches above the largest launch class (8192 paths) go out as consecutive slices on the same
+ * stream; without the quad kernels (or under STARKPERP_NO_PATH_FOLD=1) one gathered launch per level serves the call. */
+#define SP_PATH_FALSE 0
+#define SP_PATH_TRUE 1
+int sp_merkle_fold_paths_dev(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, unsigned height,
+                             const uint64_t* keys, size_t n, uint64_t* roots, uint8_t* status, void* stream);
+int sp_merkle_fold_paths(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, unsigned height,
+                         const uint64_t* keys, size_t n, uint64_t* roots, uint8_t* status);
+int sp_merkle_verify_paths(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, unsigned height,
+                           const uint64_t* keys, size_t n, const uint64_t* expected, size_t n_expected,
+                           uint8_t* verdict, uint8_t* status);
 /* Threading of the sp_tree_* calls: a tree has its own HIP stream, work buffer and mutex.  An operation holds
  * the tree's mutex from start to end and the library lock only while it enqueues; the device work of an update
  * (the level launches) runs without the library lock, so other trees and the stateless batches go on meanwhile. */

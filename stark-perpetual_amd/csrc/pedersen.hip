@@ -741,6 +741,117 @@ ped_chain_ragged_scatter_kernel(const uint64_t* __restrict__ work, const uint64_
   if (status) status[c] = st;
 }
 
+__device__ __forceinline__ bool u256_same(const u256& a, const u256& b) {
+  uint32_t d = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) d |= a.w[k] ^ b.w[k];
+  return d == 0;
+}
+// Root, status and verdict of one folded Merkle path, by its writer lane (ped_path_fold_kernel and the last launch
+// of its fallback): verdict = 1 only for status 0 and a root equal to the expected one at expect + e * estride felts
+// (estride 0: one root for the whole call).
+__device__ __forceinline__ void path_fold_result(size_t e, const u256& root, uint8_t st, uint64_t* __restrict__ roots,
+                                                 uint8_t* __restrict__ status, const uint64_t* __restrict__ expect,
+                                                 size_t estride, uint8_t* __restrict__ verdict) {
+  st_u256(roots + 4 * e, root);
+  if (status) status[e] = st;
+  if (verdict) verdict[e] = (st == SP_HASH_OK && u256_same(root, ld_u256(expect + 4 * e * estride))) ? SP_PATH_TRUE : SP_PATH_FALSE;
+}
+
+// Merkle paths (inclusion proofs) of UNEQUAL length as one launch: a sided ragged chain with the lane groups, the
+// `dup` idiom, the LDS hand-over, the block-wide loop bound and the end-of-path no-op of ped_chain_ragged_kernel.
+// Path e starts from leaves + 4 e and takes, at step j, the sibling w = siblings + 4 (off[e] + j); bit j of keys[e] -
+// the same on every lane of the group - says that the running node h is the RIGHT child at level j
+// (starkware/python/merkle_tree.py:4-26): h <- H(w, h), else h <- H(h, w).  A path of no steps folds to its leaf.
+// status[e] (optional) = OR of the steps' status bytes (the leaf is range-checked at step 0 and in a path of no
+// steps, every sibling at its step); verdict[e] (optional): see path_fold_result.
+template <int LOG_Q>
+__global__ void __launch_bounds__(256)
+ped_path_fold_kernel(const uint64_t* __restrict__ leaves, const uint64_t* __restrict__ siblings,
+                     const uint32_t* __restrict__ off, const uint64_t* __restrict__ keys, size_t n,
+                     const aff_packed* __restrict__ ped, int w0, int log2e, int nwin_plan, unsigned* __restrict__ flag,
+                     uint8_t* __restrict__ status, uint64_t* __restrict__ roots, const uint64_t* __restrict__ expect,
+                     size_t estride, uint8_t* __restrict__ verdict, int dup) {
+  constexpr int QUADS = 1 << LOG_Q, LANES = 4 * QUADS;
+  __shared__ uint64_t slot[256 / LANES][4];
+  __shared__ int block_steps;
+  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t e_raw = gt / ((size_t)LANES << dup);
+  const int g = (int)(gt % LANES), grp = (int)(threadIdx.x / LANES);
+  const bool active = e_raw < n;
+  const size_t e = active ? e_raw : n - 1;  // clamped groups repeat the last path: the same length, no write
+  const bool writer = active && g == 0 && ((gt / LANES) & (((size_t)1 << dup) - 1)) == 0;
+  const uint32_t o0 = off[e];
+  const int steps = (int)(off[e + 1] - o0);  // 0 .. 64; every group of one path (dup) reads the same two offsets
+  const uint64_t key = keys[e];
+  if (threadIdx.x == 0) block_steps = 0;
+  __syncthreads();
+  if (g == 0 && steps > 0) atomicMax(&block_steps, steps);
+  __syncthreads();
+  const int bound = block_steps;
+  const uint64_t* leaf = leaves + 4 * e;
+  uint8_t st = SP_HASH_OK;
+  if (steps == 0 && writer) {  // a path of no siblings
+    const u256 v = ld_u256(leaf);
+    if (!u256_lt(v, U256_P)) st = SP_HASH_OUT_OF_RANGE;
+    path_fold_result(e, v, st, roots, status, expect, estride, verdict);
+    if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);
+  }
+  const uint64_t* h = leaf;
+  const uint64_t* w = siblings + 4 * (size_t)o0;
+  for (int j = 0; j < bound; ++j, w += 4) {
+    const bool live = j < steps;                // the same on every lane of the group, like `right`
+    const bool right = ((key >> (j & 63)) & 1) != 0;  // j <= 63: bound <= 64
+    const uint64_t* fx = live ? (right ? w : h) : leaf;
+    const uint64_t* fy = live ? (right ? h : w) : leaf;
+    bool unhashable;
+    const u256 xa = quad_hash<LOG_Q, false>(fx, fy, 0, nullptr, 0, 0, ped, w0, log2e, nwin_plan, g, &unhashable);
+    if (live && g == 0) {
+      // every sibling is a caller's value; the running node is one only at the first step
+      if (!u256_lt(ld_u256(w), U256_P) || (j == 0 && !u256_lt(ld_u256(h), U256_P))) st |= SP_HASH_OUT_OF_RANGE;
+      else if (unhashable) st |= SP_HASH_UNHASHABLE;
+    }
+    __syncthreads();  // every lane of the block has taken its windows of this step
+    if (live && g == 0) {
+      uint32_t* sl = reinterpret_cast<uint32_t*>(slot[grp]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) sl[k] = xa.w[k];
+      if (j == steps - 1 && writer) {
+        path_fold_result(e, xa, st, roots, status, expect, estride, verdict);
+        if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);
+      }
+    }
+    __syncthreads();
+    h = slot[grp];
+  }
+}
+
+// The fallback of the Merkle paths: the last launch after the per-step launches, as ped_chain_ragged_scatter_kernel.
+// Sorted position k holds path perm[k]; its running node is work[k], the status byte of its step j is
+// step_status[step_off[j] + k]; a path of no steps is its leaf (range-checked here).
+__global__ void __launch_bounds__(256)
+ped_path_fold_scatter_kernel(const uint64_t* __restrict__ work, const uint64_t* __restrict__ leaves,
+                             const uint32_t* __restrict__ off, const uint32_t* __restrict__ perm,
+                             const uint32_t* __restrict__ step_off, const uint8_t* __restrict__ step_status, size_t n,
+                             unsigned* __restrict__ flag, uint8_t* __restrict__ status, uint64_t* __restrict__ roots,
+                             const uint64_t* __restrict__ expect, size_t estride, uint8_t* __restrict__ verdict) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const uint32_t c = perm[k];
+  const uint32_t len = off[c + 1] - off[c];
+  uint8_t st = SP_HASH_OK;
+  u256 v;
+  if (len == 0) {
+    v = ld_u256(leaves + 4 * (size_t)c);
+    if (!u256_lt(v, U256_P)) st = SP_HASH_OUT_OF_RANGE;
+    if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);  // the step launches have reported theirs
+  } else {
+    v = ld_u256(work + 4 * k);
+    for (uint32_t j = 0; j < len; ++j) st |= step_status[(size_t)step_off[j] + k];
+  }
+  path_fold_result(c, v, st, roots, status, expect, estride, verdict);
+}
+
 // The small levels of a DENSE forest (at most 2048 hashes per level: the eight-quad size class) as one launch per
 // FOUR levels: a block of 8 lane groups (256 threads = one wave per SIMD of its CU: two blocks' waves on one SIMD
 // would halve the speed of both chains) takes 2^L consecutive nodes of level j (L <= 4 levels remain inside every
@@ -1504,6 +1615,185 @@ static bool ragged_offsets_ok(const uint32_t* off, size_t n) {
   return true;
 }
 
+// ---- Merkle paths (sp_merkle_fold_paths[_dev], sp_merkle_verify_paths) ----------------------------
+static bool g_path_fold = getenv("STARKPERP_NO_PATH_FOLD") == nullptr;  // A/B switch
+// n paths: path i starts from leaves + 4 i and takes the siblings off[i] .. off[i + 1) of `siblings` (device), bit j
+// of keys[i] = the side at step j; `off` (n + 1) and `keys` (n) are validated HOST arrays.  roots, status (n bytes or
+// null), expect (+ 4 i estride, estride 0 or 1) and verdict (n bytes; both or neither) on the device.  Enqueues on
+// `st` and returns; the caller holds the context lock.
+// Fused: consecutive slices of at most chain_ragged_cap() paths, one ped_path_fold_kernel launch each; keys and
+// offsets go over in one copy.  Fallback: as enqueue_pedersen_chain_ragged - the paths sorted by falling length, step
+// j one gathered enqueue_pedersen launch over the prefix still running, the index pair of a path swapped where its
+// side bit of that step is set - and a last launch that restores the caller's order.
+int enqueue_pedersen_path_fold(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, const uint64_t* keys,
+                               size_t n, uint64_t* roots, uint8_t* status, const uint64_t* expect, size_t estride,
+                               uint8_t* verdict, hipStream_t st) {
+  if (n == 0) return SP_OK;
+  Context& c = ctx();
+  const int w0 = c.plan.bits[0], log2e = c.plan.log2e, nwin = c.plan.nwin;
+  const size_t total = off[n];
+  const size_t cap = g_path_fold ? chain_ragged_cap() : 0;
+  Scratch s;
+  char* tail = nullptr;
+  if (cap != 0) {
+    // metadata, one copy: keys[n] (64-bit) | off[n + 1]
+    std::vector<uint64_t> meta(n + (n + 2) / 2);
+    std::memcpy(meta.data(), keys, n * sizeof(uint64_t));
+    std::memcpy(meta.data() + n, off, (n + 1) * sizeof(uint32_t));
+    int rc = get_scratch_tail(1, meta.size() * sizeof(uint64_t), s, &tail, st);
+    if (rc != SP_OK) return rc;
+    SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
+    const uint64_t* d_keys = (const uint64_t*)tail;
+    const uint32_t* d_off = (const uint32_t*)(d_keys + n);
+    rc = ragged_stage_copy(meta.data(), meta.size() * sizeof(uint64_t), tail, st);
+    if (rc != SP_OK) return rc;
+    for (size_t b = 0; b < n; b += cap) {
+      const size_t m = n - b < cap ? n - b : cap;
+      int log_q = 1;  // the size classes of enqueue_pedersen_chain; m <= cap always has one
+      if (m <= g_quad_max && nwin >= 16) log_q = 3;
+      else if (m <= 2 * g_quad_max && nwin >= 8) log_q = 2;
+      int dup = 0;
+      while ((4 << (log_q + dup)) < 64 && ((m * 4) << (log_q + dup + 1)) <= 65536) ++dup;  // up to one path per wave
+      if (g_quad_no_dup) dup = 0;
+      const unsigned blocks = (unsigned)((((m * 4) << (log_q + dup)) + 255) / 256);
+      // the slice's offsets stay absolute (d_off + b), so `siblings` is not advanced
+#define SP_LAUNCH_FOLD(LOGQ)                                                                                          \
+  hipLaunchKernelGGL((ped_path_fold_kernel<LOGQ>), dim3(blocks), dim3(256), 0, st, leaves + 4 * b, siblings, d_off + b, \
+                     d_keys + b, m, c.ped, w0, log2e, nwin, s.flag, status ? status + b : nullptr, roots + 4 * b,       \
+                     expect ? expect + 4 * b * estride : nullptr, estride, verdict ? verdict + b : nullptr, dup)
+      if (log_q == 3) SP_LAUNCH_FOLD(3);
+      else if (log_q == 2) SP_LAUNCH_FOLD(2);
+      else SP_LAUNCH_FOLD(1);
+#undef SP_LAUNCH_FOLD
+      SP_HIP(hipGetLastError());
+    }
+    return SP_OK;
+  }
+  // ---- fallback ----
+  if (2 * n + total > 0x7fffffffull) { set_error("merkle paths: more than 2^31 felts"); return SP_ERR_BAD_ARGUMENT; }
+  std::vector<uint32_t> perm(n);
+  for (size_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
+  std::stable_sort(perm.begin(), perm.end(),
+                   [&](uint32_t a, uint32_t b) { return off[a + 1] - off[a] > off[b + 1] - off[b]; });
+  const size_t maxlen = off[perm[0] + 1] - off[perm[0]];
+  const size_t n_pairs = total;  // sum over the steps of the paths still running = all hashes of the call
+  // metadata, one copy: off[n + 1] | perm[n] | step_off[maxlen] | (pad to 8 bytes) | index pairs (2 x n_pairs)
+  const size_t pairs_at = (2 * n + 1 + maxlen + 1) & ~(size_t)1;
+  std::vector<uint32_t> meta(pairs_at + 2 * n_pairs);
+  std::memcpy(meta.data(), off, (n + 1) * sizeof(uint32_t));
+  std::memcpy(meta.data() + n + 1, perm.data(), n * sizeof(uint32_t));
+  uint32_t* step_off = meta.data() + 2 * n + 1;
+  uint32_t* pairs = meta.data() + pairs_at;
+  std::vector<size_t> running(maxlen, 0);  // running[j] = paths of more than j siblings
+  size_t m = n, pos = 0;
+  // work buffer: running nodes [0, n) in sorted order | the leaves [n, 2 n) | the siblings [2 n, 2 n + total)
+  for (size_t j = 0; j < maxlen; ++j) {
+    while (m > 0 && off[perm[m - 1] + 1] - off[perm[m - 1]] <= j) --m;
+    running[j] = m;
+    step_off[j] = (uint32_t)pos;
+    for (size_t k = 0; k < m; ++k) {
+      const uint32_t h = j == 0 ? (uint32_t)n + perm[k] : (uint32_t)k;    // the leaf, later the running node
+      const uint32_t w = 2 * (uint32_t)n + off[perm[k]] + (uint32_t)j;    // sibling j of the path
+      const bool right = ((keys[perm[k]] >> j) & 1) != 0;
+      pairs[2 * (pos + k)] = right ? w : h;
+      pairs[2 * (pos + k) + 1] = right ? h : w;
+    }
+    pos += m;
+  }
+  const size_t meta_bytes = (meta.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
+  const size_t stat_bytes = (n_pairs + 255) & ~(size_t)255;
+  int rc = get_scratch_tail(n, meta_bytes + stat_bytes + (2 * n + total) * 32, s, &tail, st);
+  if (rc != SP_OK) return rc;
+  SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
+  uint32_t* d_meta = (uint32_t*)tail;
+  uint8_t* d_stat = (uint8_t*)(tail + meta_bytes);
+  uint64_t* d_work = (uint64_t*)(tail + meta_bytes + stat_bytes);
+  rc = ragged_stage_copy(meta.data(), meta.size() * sizeof(uint32_t), d_meta, st);
+  if (rc != SP_OK) return rc;
+  SP_HIP(hipMemcpyAsync(d_work + 4 * n, leaves, n * 32, hipMemcpyDeviceToDevice, st));
+  if (total > 0) SP_HIP(hipMemcpyAsync(d_work + 8 * n, siblings, total * 32, hipMemcpyDeviceToDevice, st));
+  const int2* d_pairs = reinterpret_cast<const int2*>(d_meta + pairs_at);
+  for (size_t j = 0; j < maxlen; ++j) {
+    rc = enqueue_pedersen(d_work, 1, d_work, 1, d_work, 1, d_stat + step_off[j], s.flag, running[j], st, s,
+                          d_pairs + step_off[j]);
+    if (rc != SP_OK) return rc;
+  }
+  hipLaunchKernelGGL(ped_path_fold_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_work, leaves,
+                     d_meta, d_meta + n + 1, d_meta + 2 * n + 1, d_stat, n, s.flag, status, roots, expect, estride, verdict);
+  SP_HIP(hipGetLastError());
+  return SP_OK;
+}
+// Validates a path call's arguments and returns the offsets to use: `off` itself, or (off == NULL) the uniform
+// offsets i * height built in `uniform`.  nullptr: a bad argument, the text is in sp_last_error.
+static const uint32_t* path_offsets_ok(const uint32_t* off, unsigned height, const uint64_t* keys, size_t n,
+                                       std::vector<uint32_t>& uniform) {
+  if (keys == nullptr) { set_error("merkle paths: keys must not be NULL"); return nullptr; }
+  if (off == nullptr) {
+    if (height > 64) { set_error("merkle paths: height must be <= 64"); return nullptr; }
+    if (height != 0 && n > 0xffffffffull / height) { set_error("merkle paths: more than 2^32 - 1 sibling felts"); return nullptr; }
+    uniform.resize(n + 1);
+    for (size_t i = 0; i <= n; ++i) uniform[i] = (uint32_t)(i * height);
+    off = uniform.data();
+  } else {
+    if (off[0] != 0) { set_error("merkle paths: off[0] must be 0"); return nullptr; }
+    for (size_t i = 0; i < n; ++i) {
+      if (off[i + 1] < off[i]) { set_error("merkle paths: the offsets must not decrease"); return nullptr; }
+      if (off[i + 1] - off[i] > 64) { set_error("merkle paths: a path has at most 64 siblings"); return nullptr; }
+    }
+  }
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t len = off[i + 1] - off[i];
+    if (len < 64 && (keys[i] >> len) != 0) { set_error("merkle paths: a key bit at or above its path's length is set"); return nullptr; }
+  }
+  return off;
+}
+// The host-pointer calls on a host lane: leaves and siblings up, one enqueue, roots (fold) or verdicts (verify) and
+// the status bytes down.
+static int merkle_paths_host(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, unsigned height,
+                             const uint64_t* keys, size_t n, const uint64_t* expected, size_t n_expected, uint64_t* roots,
+                             uint8_t* verdict, uint8_t* status) {
+  LaneScope ls(0);  // the primary context, as sp_pedersen_chains_ragged
+  SP_REQUIRE_READY();
+  const bool verify = verdict != nullptr;
+  if (verify && n_expected != 1 && n_expected != n) { set_error("merkle paths: n_expected must be 1 or n"); return SP_ERR_BAD_ARGUMENT; }
+  if (n == 0) return SP_OK;
+  std::vector<uint32_t> uniform;
+  off = path_offsets_ok(off, height, keys, n, uniform);
+  if (off == nullptr) return SP_ERR_BAD_ARGUMENT;
+  if (ls.open() != SP_OK) return SP_ERR_HIP;
+  HostLane& L = *ls.lane;
+  const size_t total = off[n];
+  const size_t n_exp = verify ? n_expected : 0;
+  // device: leaves | siblings | expected | roots | verdict bytes | status bytes
+  const size_t in_bytes = (n + total + n_exp) * 32;
+  SP_HIP(L.io.reserve(in_bytes + n * 32 + 2 * n + 64));
+  uint64_t* d_leaves = (uint64_t*)L.io.ptr;
+  uint64_t* d_sib = d_leaves + 4 * n;
+  uint64_t* d_exp = d_sib + 4 * total;
+  uint64_t* d_roots = d_exp + 4 * n_exp;
+  uint8_t* d_ver = (uint8_t*)(d_roots + 4 * n);
+  uint8_t* d_st = d_ver + n;
+  SP_HIP(hipMemcpyAsync(d_leaves, leaves, n * 32, hipMemcpyHostToDevice, L.stream));
+  if (total > 0) SP_HIP(hipMemcpyAsync(d_sib, siblings, total * 32, hipMemcpyHostToDevice, L.stream));
+  if (verify) SP_HIP(hipMemcpyAsync(d_exp, expected, n_exp * 32, hipMemcpyHostToDevice, L.stream));
+  int rc;
+  {
+    ctx_lock lk(ctx().mu);
+    rc = enqueue_pedersen_path_fold(d_leaves, d_sib, off, keys, n, d_roots, d_st, verify ? d_exp : nullptr,
+                                    n_expected == n ? 1 : 0, verify ? d_ver : nullptr, L.stream);
+  }
+  if (rc != SP_OK) return rc;
+  if (verify) {
+    SP_HIP(hipMemcpyAsync(verdict, d_ver, n, hipMemcpyDeviceToHost, L.stream));
+    if (status) SP_HIP(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, L.stream));
+  } else {
+    SP_HIP(hipMemcpyAsync(roots, d_roots, n * 32, hipMemcpyDeviceToHost, L.stream));
+    if (status) SP_HIP(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, L.stream));
+  }
+  SP_HIP(hipStreamSynchronize(L.stream));
+  return SP_OK;
+}
+
 }  // namespace sp
 
 using namespace sp;
@@ -1722,6 +2012,38 @@ int sp_pedersen_chains_ragged(const uint64_t* elems, const uint32_t* off, size_t
     if (status) std::memcpy(status, stage + in_bytes + n * 32, n);
   }
   return SP_OK;
+}
+
+// Merkle paths folded in one launch (ped_path_fold_kernel): path i starts from leaves[i], bit l of keys[i] is the side
+// at level l.  Enqueues and returns; the HOST arrays `off` and `keys` have been copied when it does.
+int sp_merkle_fold_paths_dev(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, unsigned height,
+                             const uint64_t* keys, size_t n, uint64_t* roots, uint8_t* status, void* stream) {
+  CtxByPointer sp_ctx_sel__(leaves);  // the context of the device these pointers live on
+  SP_REQUIRE_READY();
+  if (n == 0) return SP_OK;
+  std::vector<uint32_t> uniform;
+  off = path_offsets_ok(off, height, keys, n, uniform);
+  if (off == nullptr) return SP_ERR_BAD_ARGUMENT;
+  ctx_lock lk(ctx().mu);
+  return enqueue_pedersen_path_fold(leaves, siblings, off, keys, n, roots, status, nullptr, 0, nullptr, (hipStream_t)stream);
+}
+
+// Host-pointer variants: one staged round trip on a host lane; the verifier compares on the device and brings back
+// the verdict (and status) bytes only.
+int sp_merkle_fold_paths(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, unsigned height,
+                         const uint64_t* keys, size_t n, uint64_t* roots, uint8_t* status) {
+  if (n != 0 && roots == nullptr) { set_error("merkle paths: roots must not be NULL"); return SP_ERR_BAD_ARGUMENT; }
+  return merkle_paths_host(leaves, siblings, off, height, keys, n, nullptr, 0, roots, nullptr, status);
+}
+int sp_merkle_verify_paths(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, unsigned height,
+                           const uint64_t* keys, size_t n, const uint64_t* expected, size_t n_expected,
+                           uint8_t* verdict, uint8_t* status) {
+  if (n != 0 && (verdict == nullptr || expected == nullptr)) {
+    set_error("merkle paths: expected and verdict must not be NULL");
+    return SP_ERR_BAD_ARGUMENT;
+  }
+  if (n == 0 && verdict == nullptr) return SP_OK;
+  return merkle_paths_host(leaves, siblings, off, height, keys, n, expected, n_expected, nullptr, verdict, status);
 }
 
 int sp_pedersen_chain(const uint64_t* elems, size_t n_elems, uint64_t* out, uint8_t* status) {

@@ -112,6 +112,34 @@ def pedersen_chains_ragged(chains):
     return unpack_felts(out, n)
 
 
+def merkle_fold_paths(keys, proofs):
+    """Roots of Merkle paths of any lengths 0 .. 64 in ONE library call (sp_merkle_fold_paths): proofs[i] = (leaf,
+    siblings); at level l bit l of keys[i] says whether the running node is the right child (merkle_tree.py:4-26).
+    A path of no siblings folds to its leaf.  Raises on a status like pedersen_chains_ragged."""
+    n = len(proofs)
+    assert len(keys) == n
+    if n == 0:
+        return []
+    leaves, flat, off = [], [], [0]
+    for key, (leaf, siblings) in zip(keys, proofs):
+        assert len(siblings) <= 64 and 0 <= key < (1 << len(siblings))
+        assert 0 <= leaf < FIELD_PRIME
+        assert not siblings or (min(siblings) >= 0 and max(siblings) < FIELD_PRIME)
+        leaves.append(leaf)
+        flat.extend(siblings)
+        off.append(len(flat))
+    assert off[-1] < 2**32
+    lib = _lib.ensure_init()
+    out, st = new_felts(n), new_bytes(n)
+    _lib.check(lib.sp_merkle_fold_paths(pack_felts(leaves), pack_felts(flat) if flat else None,
+                                        (ctypes.c_uint32 * (n + 1))(*off), 0, (ctypes.c_uint64 * n)(*keys), n, out, st),
+               "sp_merkle_fold_paths")
+    for code in bytes(st)[:n]:
+        if code:
+            _raise_hash_status(2 if code & 2 else 1)
+    return unpack_felts(out, n)
+
+
 def pedersen_points_many(xs, ys):
     """[pedersen_hash_as_point(x, y) ...] (signature.py:300-318) - the full affine point."""
     n = len(xs)

@@ -100,6 +100,68 @@ def pedersen_chains_ragged(words, offsets):
     return out, st
 
 
+def merkle_path_args(leaves, siblings, keys, height=None, offsets=None):
+    """The arguments of the Merkle path calls, checked: (leaves uint64[n, 4], siblings uint64[total, 4], offsets
+    uint32[n + 1] or None, height, keys uint64[n]).  Exactly one of `height` (every path has `height` siblings:
+    siblings uint64[n, height, 4] or [n * height, 4], the output of tree_prove) and `offsets` (uint32[n + 1],
+    offsets[0] = 0, non-decreasing by at most 64, offsets[n] = rows of siblings) is given.  Pure host code."""
+    lv = _felts(leaves)
+    n = lv.shape[0]
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    assert k.ndim == 1 and k.shape[0] == n, "keys are uint64[n]"
+    assert (height is None) != (offsets is None), "give either height or offsets"
+    sib = np.ascontiguousarray(siblings, dtype=np.uint64)
+    if height is not None:
+        height = int(height)
+        assert 0 <= height <= 64, "height is 0 .. 64"
+        sib = sib.reshape(n * height, 4)
+        return lv, sib, None, height, k
+    assert sib.ndim == 2 and sib.shape[1] == 4, "felts are uint64[n, 4]"
+    off = np.ascontiguousarray(offsets, dtype=np.uint32)
+    assert off.ndim == 1 and off.shape[0] == n + 1, "offsets are uint32[n + 1]"
+    assert int(off[-1]) == sib.shape[0], "offsets[n] must be the number of sibling rows"
+    return lv, sib, off, 0, k
+
+
+def uniform_path_offsets(n, height) -> np.ndarray:
+    """The offsets that describe n paths of `height` siblings each: what the library builds when offsets is None."""
+    return (np.arange(n + 1, dtype=np.uint64) * np.uint64(height)).astype(np.uint32)
+
+
+def merkle_fold_paths(leaves, siblings, keys, height=None, offsets=None):
+    """Merkle paths folded on the device in one call (sp_merkle_fold_paths): path i starts from leaves[i]; at level l
+    bit l of keys[i] says whether the running node is the right child (merkle_tree.py:4-26), node = H(left, right).
+    Arguments as merkle_path_args.  Returns (roots uint64[n, 4], status uint8[n]); like pedersen_chains_ragged it
+    does not raise for a value outside [0, p): status[i] carries the HASH_* bits of path i alone."""
+    lv, sib, off, height, k = merkle_path_args(leaves, siblings, keys, height, offsets)
+    n = lv.shape[0]
+    roots = np.empty((n, 4), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    if n == 0:
+        return roots, st
+    _lib.check(_lib.ensure_init().sp_merkle_fold_paths(_ptr(lv), _ptr(sib), None if off is None else _ptr(off), height,
+                                                       _ptr(k), n, _ptr(roots), _ptr(st)), "sp_merkle_fold_paths")
+    return roots, st
+
+
+def merkle_verify_paths(leaves, siblings, keys, expected, height=None, offsets=None):
+    """Inclusion proofs checked on the device in one call (sp_merkle_verify_paths): expected = uint64[4] / [1, 4]
+    (one root for all paths) or uint64[n, 4].  Returns (verdict bool[n], status uint8[n]); verdict[i] is True only
+    if status[i] is 0 and path i folds to its expected root.  Only these bytes come back from the device."""
+    lv, sib, off, height, k = merkle_path_args(leaves, siblings, keys, height, offsets)
+    n = lv.shape[0]
+    exp = np.ascontiguousarray(expected, dtype=np.uint64).reshape(-1, 4)
+    assert exp.shape[0] in (1, n), "expected holds 1 or n roots"
+    verdict = np.zeros(n, dtype=np.uint8)
+    st = np.zeros(n, dtype=np.uint8)
+    if n == 0:
+        return verdict.astype(bool), st
+    _lib.check(_lib.ensure_init().sp_merkle_verify_paths(_ptr(lv), _ptr(sib), None if off is None else _ptr(off), height,
+                                                         _ptr(k), n, _ptr(exp), exp.shape[0], _ptr(verdict), _ptr(st)),
+               "sp_merkle_verify_paths")
+    return verdict == 1, st
+
+
 def verify_codes(z, r, s, qx, qy=None, key_tables=None) -> np.ndarray:
     """Result codes (include/starkperp.h SP_VERIFY_*) of verify(z, r, s, key) per row; qy None = x-only
     keys (signature.py:229-238).  key_tables as in starkperp.batch.verify_codes."""

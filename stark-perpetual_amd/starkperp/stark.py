@@ -2,6 +2,8 @@
 -> commit -> FRI folds with per-layer commits.  Build-defined (the reference has no prover); every
 commitment hash is the reference's pedersen_hash.  Columns live in HBM as torch int64 [n, 4]
 tensors (four little-endian 64-bit limbs per felt); torch is only the allocator / stream owner."""
+from typing import List, Tuple
+
 from . import _lib
 from ._lib import pack_felts
 
@@ -392,6 +394,70 @@ def prove_trace(trace, air: str, n_queries: int = 8, seed: int = 0, final_log: i
         queries.append(entry)
     return {"n": n, "air": air, "seed": seed, "shift": shift, "public_inputs": list(public_inputs),
             "trace_root": root_t, "layer_roots": roots, "final_layer": final, "queries": queries}
+
+
+def check_merkle_openings(proof) -> List[Tuple[str, bool]]:
+    """The Merkle part of a verifier, on the GPU: does every opening of `proof` (from prove_trace or one of its
+    wrappers: prove, prove_ec_ladders, prove_ecdsa, prove_range_checks) fold to the commitment it claims?
+
+    Returns one (label, ok) per opening in proof order, labelled "q3/trace/row 517" (a trace row against
+    trace_root) or "q3/layer 2/pos 40" (a FRI layer value against layer_roots[2]).  Two library calls in all: the
+    leaves of the opened trace rows - the left fold of the row's values, as commit_rows - are hashed by one
+    pedersen_chains_ragged call, and every path of the proof, the trace openings of height log2(M) and the layer
+    openings of falling heights, goes to ONE sp_merkle_verify_paths call with offsets and per-item expected roots.
+    A value outside [0, p) makes its opening False.
+
+    This checks the Merkle part ONLY.  The AIR relation between the opened rows and the composition column, the FRI
+    fold consistency, the final layer's degree, the query positions and the transcript stay with
+    oracle/stark_ref.verify_proof: a proof whose openings are all True here can still be rejected there."""
+    import numpy as np
+    from . import batch_np
+    P = FIELD_PRIME
+    felt = lambda v: v if 0 <= v < 2**256 else P  # unrepresentable: p itself, which the device flags as out of range
+    labels, keys, expected, paths = [], [], [], []
+    rows, leaf_slot = [], []  # the chains of the trace rows; leaf_slot[i] = index into rows or None (leaf given)
+    leaves = []
+    for qi, q in enumerate(proof["queries"]):
+        for t in q["trace"]:
+            labels.append("q%d/trace/row %d" % (qi, t["row"]))
+            keys.append(t["row"])
+            expected.append(proof["trace_root"])
+            paths.append([felt(v) for v in t["path"]])
+            leaf_slot.append(len(rows))
+            rows.append([felt(v) for v in t["values"]])
+            leaves.append(0)
+        for k, pair in enumerate(q["layers"]):
+            for o in pair:
+                labels.append("q%d/layer %d/pos %d" % (qi, k, o["pos"]))
+                keys.append(o["pos"])
+                expected.append(proof["layer_roots"][k])
+                paths.append([felt(v) for v in o["path"]])
+                leaf_slot.append(None)
+                leaves.append(felt(o["value"]))
+    n = len(labels)
+    if n == 0:
+        return []
+    leaf_arr = batch_np.felts_from_ints(leaves)
+    leaf_bad = np.zeros(n, dtype=bool)
+    if rows:
+        row_off = np.zeros(len(rows) + 1, dtype=np.uint32)
+        row_off[1:] = np.cumsum([len(r) for r in rows])
+        hashed, row_st = batch_np.pedersen_chains_ragged(batch_np.felts_from_ints([v for r in rows for v in r]), row_off)
+        slots = np.array([i for i, s in enumerate(leaf_slot) if s is not None])
+        leaf_arr[slots] = hashed
+        leaf_bad[slots] = row_st != 0
+        leaf_arr[slots[row_st != 0]] = 0  # what a failed chain leaves is unspecified; the opening is False anyway
+    # a position that does not fit its path's height cannot be opened by it
+    fits = np.array([len(p) <= 64 and 0 <= k < (1 << len(p)) for k, p in zip(keys, paths)])
+    off = np.zeros(n + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(p) if f else 0 for p, f in zip(paths, fits)])
+    flat = [v for p, f in zip(paths, fits) if f for v in p]
+    sib = batch_np.felts_from_ints(flat) if flat else np.zeros((0, 4), dtype=np.uint64)
+    key_arr = np.array([k if f else 0 for k, f in zip(keys, fits)], dtype=np.uint64)
+    verdict, _ = batch_np.merkle_verify_paths(leaf_arr, sib, key_arr, batch_np.felts_from_ints([felt(v) for v in expected]),
+                                              offsets=off)
+    ok = verdict & fits & ~leaf_bad
+    return list(zip(labels, [bool(v) for v in ok]))
 
 
 # ---- the range-check builtin's encoding and ONE trace for the three builtins (SURVEY 8(f) N4) --------------------

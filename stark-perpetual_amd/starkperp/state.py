@@ -169,6 +169,24 @@ class SparseMerkleTree:
             out.append((node, siblings))
         return out
 
+    def verify(self, keys: Sequence[int], proofs: Sequence[Tuple[int, Sequence[int]]]) -> List[bool]:
+        """Checks inclusion proofs (the shape `prove` returns) against the tree's CURRENT root: True where the proof
+        has this tree's height, its key and values are in range and it folds to the root.  One `hash_many` call per
+        level over all proofs."""
+        assert len(keys) == len(proofs)
+        good = [i for i, (k, p) in enumerate(zip(keys, proofs)) if _proof_well_formed(self.height, k, p)]
+        nodes = [proofs[i][0] for i in good]
+        for level in range(self.height):
+            sibs = [proofs[i][1][level] for i in good]
+            bits = [(keys[i] >> level) & 1 for i in good]
+            lefts = [s if b else n for n, s, b in zip(nodes, sibs, bits)]
+            rights = [n if b else s for n, s, b in zip(nodes, sibs, bits)]
+            nodes = list(self.hash_many(lefts, rights)) if good else []
+        out = [False] * len(keys)
+        for i, node in zip(good, nodes):
+            out[i] = node == self.root
+        return out
+
 
 def facts_of(witness) -> Dict[int, Tuple[int, int]]:
     """Witness records -> {node: (left, right)}: the shape of program_input['merkle_facts'] (main.cairo:39-40)."""
@@ -182,6 +200,21 @@ def proof_root(key: int, leaf: int, siblings: Sequence[int], hash_many) -> int:
         left, right = (sib, node) if (key >> level) & 1 else (node, sib)
         node = hash_many([left], [right])[0]
     return node
+
+
+def proof_roots_many(keys: Sequence[int], proofs: Sequence[Tuple[int, Sequence[int]]]) -> List[int]:
+    """[proof_root(key, leaf, siblings, ...)] for proofs of any lengths in ONE library call (sp_merkle_fold_paths):
+    every path is folded on the device, the call lasting as long as its longest path."""
+    return batch.merkle_fold_paths(list(keys), list(proofs))
+
+
+def _proof_well_formed(height: int, key, proof) -> bool:
+    """A proof that can belong to a tree of `height` at all: `height` siblings, the key inside the tree, every value
+    a field element."""
+    leaf, siblings = proof
+    if len(siblings) != height or not 0 <= key < (1 << height):
+        return False
+    return all(0 <= v < batch.FIELD_PRIME for v in [leaf, *siblings])
 
 
 class LibrarySparseTree:
@@ -278,6 +311,24 @@ class LibrarySparseTree:
         leaves, siblings = batch_np.tree_prove(self, np.array(keys, dtype=np.uint64))
         leaves, flat, h = batch_np.ints_from_felts(leaves), batch_np.ints_from_felts(siblings), self.height
         return [(leaf, flat[i * h:(i + 1) * h]) for i, leaf in enumerate(leaves)]
+
+    def verify(self, keys: Sequence[int], proofs: Sequence[Tuple[int, Sequence[int]]]) -> List[bool]:
+        """As SparseMerkleTree.verify, against the tree's current root (sp_tree_root), every well-formed proof folded
+        and compared on the device in one call (sp_merkle_verify_paths): only the verdict bytes come back."""
+        import numpy as np
+        from . import batch_np
+        assert len(keys) == len(proofs)
+        good = [i for i, (k, p) in enumerate(zip(keys, proofs)) if _proof_well_formed(self.height, k, p)]
+        out = [False] * len(keys)
+        if not good:
+            return out
+        leaves = batch_np.felts_from_ints([proofs[i][0] for i in good])
+        siblings = batch_np.felts_from_ints([v for i in good for v in proofs[i][1]])
+        verdict, _ = batch_np.merkle_verify_paths(leaves, siblings, np.array([keys[i] for i in good], dtype=np.uint64),
+                                                  batch_np.felts_from_ints([self.root]), height=self.height)
+        for i, ok in zip(good, verdict.tolist()):
+            out[i] = ok
+        return out
 
     def close(self):
         if self._handle is not None:
