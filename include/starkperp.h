@@ -226,7 +226,7 @@ int sp_tree_witness(int tree, const uint64_t* keys, size_t n, size_t capacity, u
  * sp_tree_root.  A key out of range or an unknown handle: SP_ERR_BAD_ARGUMENT, nothing written.  Same locking and
  * copy-back as sp_tree_witness; n x height (key, level) pairs must stay below 2^31. */
 int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, uint64_t* siblings);
-/* Verifying inclusion proofs: Merkle paths folded on the device, all of a call in ONE launch (ped_path_fold_kernel)
+/* Verifying inclusion proofs: Merkle paths folded on the device, all of a call in ONE launch (ped_fold_ragged_kernel)
  * that lasts as long as its longest path.  node = pedersen_hash(left, right) (signature.py:296-318); bit l of keys[i]
  * says whether the running node is the RIGHT child at level l (starkware/python/merkle_tree.py:4-26,
  * state/state.cairo:155-173): h <- H(sibling, h) if it is set, h <- H(h, sibling) if not, starting from h = leaves[i].

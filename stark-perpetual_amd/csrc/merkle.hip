@@ -21,29 +21,9 @@
 #include <vector>
 
 #include "context.hpp"
+#include "pedersen.hpp"
 
 namespace sp {
-
-struct Scratch {
-  int32_t *X, *ZZ, *Pre;
-  unsigned* flag;
-};
-int enqueue_pedersen(const uint64_t* x, size_t xs, const uint64_t* y, size_t ys, uint64_t* out,
-                     size_t os, uint8_t* status, unsigned* flag, size_t n, hipStream_t st,
-                     const Scratch& s, const int2* src);
-int get_scratch_public(size_t n, Scratch& s, hipStream_t st);
-int enqueue_partial_points(const uint64_t* felts, int count, aff_packed* out, hipStream_t st, bool* usable);
-int enqueue_pedersen_sparse(const uint64_t* x, const uint64_t* y, uint64_t* out, unsigned* flag, size_t n,
-                            hipStream_t st, const Scratch& s, const int2* src, const aff_packed* cpts);
-struct PathLevels {  // pedersen.hip ped_path_kernel
-  int first, n_levels;
-  int val_base[66];
-  unsigned src_off[66];
-};
-int enqueue_pedersen_path(uint64_t* felts, const uint64_t* emp, unsigned* flag, size_t n, hipStream_t st,
-                          const int2* src_all, const PathLevels& pl, const aff_packed* cpts_tree, bool* done);
-int enqueue_pedersen_chain_ragged(const uint64_t* elems, const uint32_t* off, size_t n, uint64_t* out, uint8_t* status,
-                                  hipStream_t st);
 
 static DeviceBuffer g_sparse_buf;
 // empty-subtree roots are a pure function of the empty leaf: cached on the host per leaf value

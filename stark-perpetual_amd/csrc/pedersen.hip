@@ -22,7 +22,9 @@
 #include <vector>
 
 #include "context.hpp"
+#include "pedersen.hpp"
 #include "quad.hpp"
+#include "ragged_plan.hpp"
 
 #ifndef SP_ACC_WAVES
 #define SP_ACC_WAVES 1
@@ -552,12 +554,7 @@ ped_quad_kernel(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, 
 // table, or the level's empty-subtree root) and the child lists are independent of the chain.  Every node value is
 // also written to `felts` for the insertion into the table.  Saves the launch boundary and the store -> load round
 // trip through HBM between two levels.  pl.val_base / pl.src_off are merkle.hip's TreeLevels fields; level
-// `pl.first` is the children's level of the first hash.
-struct PathLevels {
-  int first, n_levels;
-  int val_base[66];
-  unsigned src_off[66];
-};
+// `pl.first` is the children's level of the first hash (PathLevels: pedersen.hpp).
 template <int LOG_Q, bool SPARSE>
 __global__ void __launch_bounds__(256)
 ped_path_kernel(uint64_t* __restrict__ felts, const uint64_t* __restrict__ emp, size_t n,
@@ -648,130 +645,50 @@ ped_chain_kernel(const uint64_t* __restrict__ first, const uint64_t* __restrict_
   }
 }
 
-// Hash chains of UNEQUAL length as one launch: the lane groups, the `dup` idiom and the LDS hand-over of
-// ped_chain_kernel, with the chains packed chain-major (CSR): chain e owns the felts off[e] .. off[e + 1) of `elems`
-// and folds them from the left; a chain of one word is that word.  The loop holds barriers, so its bound is the
-// same for the whole block: the largest step count among the block's chains (an LDS maximum) - a block of short
-// chains retires early.  A group whose chain has ended goes on hashing its own first word (a harmless operand: full
-// execution mask for the lane exchanges of quad_hash, and nothing is read behind the chain's last word), arrives at
-// both barriers and writes nothing more: neither its slot, nor `out`, nor status.  status[e] (optional) = OR of the
-// steps' status bytes; of the 2^dup groups that share a chain only the first one writes.
-template <int LOG_Q>
-__global__ void __launch_bounds__(256)
-ped_chain_ragged_kernel(const uint64_t* __restrict__ elems, const uint32_t* __restrict__ off, size_t n,
-                        const aff_packed* __restrict__ ped, int w0, int log2e, int nwin_plan,
-                        unsigned* __restrict__ flag, uint8_t* __restrict__ status, uint64_t* __restrict__ out, int dup) {
-  constexpr int QUADS = 1 << LOG_Q, LANES = 4 * QUADS;
-  __shared__ uint64_t slot[256 / LANES][4];
-  __shared__ int block_steps;
-  const size_t gt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t e_raw = gt / ((size_t)LANES << dup);
-  const int g = (int)(gt % LANES), grp = (int)(threadIdx.x / LANES);
-  const bool active = e_raw < n;
-  const size_t e = active ? e_raw : n - 1;  // clamped groups repeat the last chain: the same length, no write
-  const bool writer = active && g == 0 && ((gt / LANES) & (((size_t)1 << dup) - 1)) == 0;
-  const uint32_t o0 = off[e];
-  const int steps = (int)(off[e + 1] - o0) - 1;  // every group of one chain (dup) reads the same two offsets
-  if (threadIdx.x == 0) block_steps = 0;
-  __syncthreads();
-  if (g == 0 && steps > 0) atomicMax(&block_steps, steps);
-  __syncthreads();
-  const int bound = block_steps;
-  const uint64_t* e0 = elems + 4 * (size_t)o0;
-  uint8_t st = SP_HASH_OK;
-  if (steps == 0 && writer) {  // a chain of one word
-    const u256 v = ld_u256(e0);
-    if (!u256_lt(v, U256_P)) st = SP_HASH_OUT_OF_RANGE;
-    st_u256(out + 4 * e, v);
-    if (status) status[e] = st;
-    if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);
-  }
-  const uint64_t* h = e0;
-  const uint64_t* w = e0 + 4;
-  for (int j = 0; j < bound; ++j, w += 4) {
-    const bool live = j < steps;  // the same on every lane of the group
-    const uint64_t* fx = live ? h : e0;
-    const uint64_t* fy = live ? w : e0;
-    bool unhashable;
-    const u256 xa = quad_hash<LOG_Q, false>(fx, fy, 0, nullptr, 0, 0, ped, w0, log2e, nwin_plan, g, &unhashable);
-    if (live && g == 0) {
-      // every word is a caller's value; the running hash is one only at the first step
-      if (!u256_lt(ld_u256(w), U256_P) || (j == 0 && !u256_lt(ld_u256(h), U256_P))) st |= SP_HASH_OUT_OF_RANGE;
-      else if (unhashable) st |= SP_HASH_UNHASHABLE;
-    }
-    __syncthreads();  // every lane of the block has taken its windows of this step
-    if (live && g == 0) {
-      uint32_t* sl = reinterpret_cast<uint32_t*>(slot[grp]);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) sl[k] = xa.w[k];
-      if (j == steps - 1 && writer) {
-        st_u256(out + 4 * e, xa);
-        if (status) status[e] = st;
-        if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);
-      }
-    }
-    __syncthreads();
-    h = slot[grp];
-  }
-}
-
-// The fallback of the ragged chains (no fused kernel for the plan or the switches): the last launch after the
-// per-step launches.  Sorted position k holds chain perm[k]; its running hash is work[k], the status byte of its
-// step j is step_status[step_off[j] + k]; a chain of one word is copied (and range-checked) here.
-__global__ void __launch_bounds__(256)
-ped_chain_ragged_scatter_kernel(const uint64_t* __restrict__ work, const uint64_t* __restrict__ elems,
-                                const uint32_t* __restrict__ off, const uint32_t* __restrict__ perm,
-                                const uint32_t* __restrict__ step_off, const uint8_t* __restrict__ step_status, size_t n,
-                                unsigned* __restrict__ flag, uint8_t* __restrict__ status, uint64_t* __restrict__ out) {
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const uint32_t c = perm[k];
-  const uint32_t o0 = off[c], len = off[c + 1] - o0;
-  uint8_t st = SP_HASH_OK;
-  u256 v;
-  if (len == 1) {
-    v = ld_u256(elems + 4 * (size_t)o0);
-    if (!u256_lt(v, U256_P)) st = SP_HASH_OUT_OF_RANGE;
-    if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);  // the step launches have reported theirs
-  } else {
-    v = ld_u256(work + 4 * k);
-    for (uint32_t j = 1; j < len; ++j) st |= step_status[(size_t)step_off[j] + k];
-  }
-  st_u256(out + 4 * (size_t)c, v);
-  if (status) status[c] = st;
-}
-
 __device__ __forceinline__ bool u256_same(const u256& a, const u256& b) {
   uint32_t d = 0;
 #pragma unroll
   for (int k = 0; k < 8; ++k) d |= a.w[k] ^ b.w[k];
   return d == 0;
 }
-// Root, status and verdict of one folded Merkle path, by its writer lane (ped_path_fold_kernel and the last launch
-// of its fallback): verdict = 1 only for status 0 and a root equal to the expected one at expect + e * estride felts
-// (estride 0: one root for the whole call).
-__device__ __forceinline__ void path_fold_result(size_t e, const u256& root, uint8_t st, uint64_t* __restrict__ roots,
-                                                 uint8_t* __restrict__ status, const uint64_t* __restrict__ expect,
-                                                 size_t estride, uint8_t* __restrict__ verdict) {
-  st_u256(roots + 4 * e, root);
+// Value, status and verdict of one ragged walk, by its writer lane (ped_fold_ragged_kernel and the last launch of its
+// fallback).  Paths (SIDED) have a verdict: 1 only for status 0 and a root equal to the expected one at
+// expect + e * estride felts (estride 0: one root for the whole call); chains have none, and nothing of it is compiled.
+template <bool SIDED>
+__device__ __forceinline__ void fold_result(size_t e, const u256& v, uint8_t st, uint64_t* __restrict__ out,
+                                            uint8_t* __restrict__ status, const uint64_t* __restrict__ expect,
+                                            size_t estride, uint8_t* __restrict__ verdict) {
+  st_u256(out + 4 * e, v);
   if (status) status[e] = st;
-  if (verdict) verdict[e] = (st == SP_HASH_OK && u256_same(root, ld_u256(expect + 4 * e * estride))) ? SP_PATH_TRUE : SP_PATH_FALSE;
+  if constexpr (SIDED) {
+    if (verdict) verdict[e] = (st == SP_HASH_OK && u256_same(v, ld_u256(expect + 4 * e * estride))) ? SP_PATH_TRUE : SP_PATH_FALSE;
+  }
 }
 
-// Merkle paths (inclusion proofs) of UNEQUAL length as one launch: a sided ragged chain with the lane groups, the
-// `dup` idiom, the LDS hand-over, the block-wide loop bound and the end-of-path no-op of ped_chain_ragged_kernel.
-// Path e starts from leaves + 4 e and takes, at step j, the sibling w = siblings + 4 (off[e] + j); bit j of keys[e] -
-// the same on every lane of the group - says that the running node h is the RIGHT child at level j
-// (starkware/python/merkle_tree.py:4-26): h <- H(w, h), else h <- H(h, w).  A path of no steps folds to its leaf.
-// status[e] (optional) = OR of the steps' status bytes (the leaf is range-checked at step 0 and in a path of no
-// steps, every sibling at its step); verdict[e] (optional): see path_fold_result.
-template <int LOG_Q>
+// Ragged walks - hash chains of UNEQUAL length and Merkle paths (inclusion proofs) of unequal length - as one launch:
+// the lane groups, the `dup` idiom and the LDS hand-over of ped_chain_kernel, with the walks packed CSR: walk e owns
+// the felts off[e] .. off[e + 1) of `words`.
+//   chain (SIDED = false)  folds its felts from the left: start value = the first of them, steps = len - 1, a chain of
+//                          one word is that word; leaves, keys, expect and verdict are not read
+//   path (SIDED = true)    starts from leaves + 4 e and takes, at step j, the sibling w = words + 4 (off[e] + j):
+//                          steps = len (0 .. 64); bit j of keys[e] - the same on every lane of the group - says that the
+//                          running node h is the RIGHT child at level j (starkware/python/merkle_tree.py:4-26):
+//                          h <- H(w, h), else h <- H(h, w).  A path of no steps folds to its leaf.
+// So a chain is a path with key = 0, leaf = words[off[e]], the first sibling at off[e] + 1 and steps = len - 1; the
+// differences are compile-time, the loop is one text.  The loop holds barriers, so its bound is the same for the whole
+// block: the largest step count among the block's walks (an LDS maximum) - a block of short walks retires early.  A
+// group whose walk has ended goes on hashing its own start value (a harmless operand: full execution mask for the
+// lane exchanges of quad_hash, and nothing is read behind the walk's last word), arrives at both barriers and writes
+// nothing more: neither its slot, nor `out`, nor status.  status[e] (optional) = OR of the steps' status bytes (the
+// start value is range-checked at step 0 and in a walk of no steps, every word at its step); verdict[e] (optional,
+// paths): see fold_result.  Of the 2^dup groups that share a walk only the first one writes.
+template <int LOG_Q, bool SIDED>
 __global__ void __launch_bounds__(256)
-ped_path_fold_kernel(const uint64_t* __restrict__ leaves, const uint64_t* __restrict__ siblings,
-                     const uint32_t* __restrict__ off, const uint64_t* __restrict__ keys, size_t n,
-                     const aff_packed* __restrict__ ped, int w0, int log2e, int nwin_plan, unsigned* __restrict__ flag,
-                     uint8_t* __restrict__ status, uint64_t* __restrict__ roots, const uint64_t* __restrict__ expect,
-                     size_t estride, uint8_t* __restrict__ verdict, int dup) {
+ped_fold_ragged_kernel(const uint64_t* __restrict__ leaves, const uint64_t* __restrict__ words,
+                       const uint32_t* __restrict__ off, const uint64_t* __restrict__ keys, size_t n,
+                       const aff_packed* __restrict__ ped, int w0, int log2e, int nwin_plan, unsigned* __restrict__ flag,
+                       uint8_t* __restrict__ status, uint64_t* __restrict__ out, const uint64_t* __restrict__ expect,
+                       size_t estride, uint8_t* __restrict__ verdict, int dup) {
   constexpr int QUADS = 1 << LOG_Q, LANES = 4 * QUADS;
   __shared__ uint64_t slot[256 / LANES][4];
   __shared__ int block_steps;
@@ -779,35 +696,37 @@ ped_path_fold_kernel(const uint64_t* __restrict__ leaves, const uint64_t* __rest
   const size_t e_raw = gt / ((size_t)LANES << dup);
   const int g = (int)(gt % LANES), grp = (int)(threadIdx.x / LANES);
   const bool active = e_raw < n;
-  const size_t e = active ? e_raw : n - 1;  // clamped groups repeat the last path: the same length, no write
+  const size_t e = active ? e_raw : n - 1;  // clamped groups repeat the last walk: the same length, no write
   const bool writer = active && g == 0 && ((gt / LANES) & (((size_t)1 << dup) - 1)) == 0;
   const uint32_t o0 = off[e];
-  const int steps = (int)(off[e + 1] - o0);  // 0 .. 64; every group of one path (dup) reads the same two offsets
-  const uint64_t key = keys[e];
+  // every group of one walk (dup) reads the same two offsets
+  const int steps = (int)(off[e + 1] - o0) - (SIDED ? 0 : 1);
+  uint64_t key = 0;
+  if constexpr (SIDED) key = keys[e];
   if (threadIdx.x == 0) block_steps = 0;
   __syncthreads();
   if (g == 0 && steps > 0) atomicMax(&block_steps, steps);
   __syncthreads();
   const int bound = block_steps;
-  const uint64_t* leaf = leaves + 4 * e;
+  const uint64_t* leaf = SIDED ? leaves + 4 * e : words + 4 * (size_t)o0;
   uint8_t st = SP_HASH_OK;
-  if (steps == 0 && writer) {  // a path of no siblings
+  if (steps == 0 && writer) {  // a walk of no steps
     const u256 v = ld_u256(leaf);
     if (!u256_lt(v, U256_P)) st = SP_HASH_OUT_OF_RANGE;
-    path_fold_result(e, v, st, roots, status, expect, estride, verdict);
+    fold_result<SIDED>(e, v, st, out, status, expect, estride, verdict);
     if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);
   }
   const uint64_t* h = leaf;
-  const uint64_t* w = siblings + 4 * (size_t)o0;
+  const uint64_t* w = SIDED ? words + 4 * (size_t)o0 : leaf + 4;
   for (int j = 0; j < bound; ++j, w += 4) {
-    const bool live = j < steps;                // the same on every lane of the group, like `right`
-    const bool right = ((key >> (j & 63)) & 1) != 0;  // j <= 63: bound <= 64
+    const bool live = j < steps;                                // the same on every lane of the group, like `right`
+    const bool right = SIDED && ((key >> (j & 63)) & 1) != 0;  // j <= 63: a path's bound is <= 64
     const uint64_t* fx = live ? (right ? w : h) : leaf;
     const uint64_t* fy = live ? (right ? h : w) : leaf;
     bool unhashable;
     const u256 xa = quad_hash<LOG_Q, false>(fx, fy, 0, nullptr, 0, 0, ped, w0, log2e, nwin_plan, g, &unhashable);
     if (live && g == 0) {
-      // every sibling is a caller's value; the running node is one only at the first step
+      // every word is a caller's value; the running value is one only at the first step
       if (!u256_lt(ld_u256(w), U256_P) || (j == 0 && !u256_lt(ld_u256(h), U256_P))) st |= SP_HASH_OUT_OF_RANGE;
       else if (unhashable) st |= SP_HASH_UNHASHABLE;
     }
@@ -817,7 +736,7 @@ ped_path_fold_kernel(const uint64_t* __restrict__ leaves, const uint64_t* __rest
 #pragma unroll
       for (int k = 0; k < 8; ++k) sl[k] = xa.w[k];
       if (j == steps - 1 && writer) {
-        path_fold_result(e, xa, st, roots, status, expect, estride, verdict);
+        fold_result<SIDED>(e, xa, st, out, status, expect, estride, verdict);
         if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);
       }
     }
@@ -826,30 +745,31 @@ ped_path_fold_kernel(const uint64_t* __restrict__ leaves, const uint64_t* __rest
   }
 }
 
-// The fallback of the Merkle paths: the last launch after the per-step launches, as ped_chain_ragged_scatter_kernel.
-// Sorted position k holds path perm[k]; its running node is work[k], the status byte of its step j is
-// step_status[step_off[j] + k]; a path of no steps is its leaf (range-checked here).
+// The fallback of the ragged walks (no fused kernel for the plan or the switches; ragged_plan.hpp): the last launch
+// after the per-step launches.  Sorted position k holds walk perm[k]; its running value is work[k], the status byte
+// of its step s is step_status[step_off[s] + k]; a walk of no steps is its start value (`lone` + 4 c for a path,
+// `lone` + 4 off[c] for a chain), copied and range-checked here.
 __global__ void __launch_bounds__(256)
-ped_path_fold_scatter_kernel(const uint64_t* __restrict__ work, const uint64_t* __restrict__ leaves,
-                             const uint32_t* __restrict__ off, const uint32_t* __restrict__ perm,
-                             const uint32_t* __restrict__ step_off, const uint8_t* __restrict__ step_status, size_t n,
-                             unsigned* __restrict__ flag, uint8_t* __restrict__ status, uint64_t* __restrict__ roots,
-                             const uint64_t* __restrict__ expect, size_t estride, uint8_t* __restrict__ verdict) {
+ped_fold_ragged_scatter_kernel(const uint64_t* __restrict__ work, const uint64_t* __restrict__ lone, bool sided,
+                               const uint32_t* __restrict__ off, const uint32_t* __restrict__ perm,
+                               const uint32_t* __restrict__ step_off, const uint8_t* __restrict__ step_status, size_t n,
+                               unsigned* __restrict__ flag, uint8_t* __restrict__ status, uint64_t* __restrict__ out,
+                               const uint64_t* __restrict__ expect, size_t estride, uint8_t* __restrict__ verdict) {
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   const uint32_t c = perm[k];
-  const uint32_t len = off[c + 1] - off[c];
+  const uint32_t o0 = off[c], steps = off[c + 1] - o0 - (sided ? 0 : 1);
   uint8_t st = SP_HASH_OK;
   u256 v;
-  if (len == 0) {
-    v = ld_u256(leaves + 4 * (size_t)c);
+  if (steps == 0) {
+    v = ld_u256(lone + 4 * (size_t)(sided ? c : o0));
     if (!u256_lt(v, U256_P)) st = SP_HASH_OUT_OF_RANGE;
     if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);  // the step launches have reported theirs
   } else {
     v = ld_u256(work + 4 * k);
-    for (uint32_t j = 0; j < len; ++j) st |= step_status[(size_t)step_off[j] + k];
+    for (uint32_t s = 0; s < steps; ++s) st |= step_status[(size_t)step_off[s] + k];
   }
-  path_fold_result(c, v, st, roots, status, expect, estride, verdict);
+  fold_result<true>(c, v, st, out, status, expect, estride, verdict);  // a chain's verdict pointer is null
 }
 
 // The small levels of a DENSE forest (at most 2048 hashes per level: the eight-quad size class) as one launch per
@@ -1135,16 +1055,51 @@ static bool g_level_split = getenv("STARKPERP_NO_LEVEL_SPLIT") == nullptr;
 static bool g_quad_no_dup = getenv("STARKPERP_QUAD_NO_DUP") != nullptr;
 static bool g_sparse_enabled = getenv("STARKPERP_NO_SPARSE_LEVELS") == nullptr;  // constant points of sparse levels
 static size_t g_quad_max = getenv("STARKPERP_QUAD_MAX") ? (size_t)atoll(getenv("STARKPERP_QUAD_MAX")) : 2048;
-// ---- host-side drivers -------------------------------------------------------------------------
-struct Scratch {
-  int32_t *X, *ZZ, *Pre;
-  unsigned* flag;
+// ---- the launch shape of the latency kernels ---------------------------------------------------
+// Quad-parallel latency kernels serve a launch while it fits one wave per SIMD: 8 quads per hash up to 2048 hashes,
+// 4 up to 4096 (same 18 rounds while nwin <= 20), 2 up to 8192; every quad needs at least two windows.  The one copy
+// of these thresholds: most hashes (chains, paths) of one launch the 2^log_q-quad kernels take under a plan of nwin
+// windows and the switches (0: that class is off).
+static size_t quad_class_max(int log_q, int nwin) {
+  if (!g_quad_enabled || nwin > 64) return 0;
+  if (log_q == 3) return nwin >= 16 ? g_quad_max : 0;
+  if (log_q == 2) return nwin >= 8 ? 2 * g_quad_max : 0;
+  return nwin >= 4 && g_quad2_enabled ? 4 * g_quad_max : 0;
+}
+// log_q = the widest class that takes n (0: none - not a launch for the quad kernels); dup: 2^dup lane groups compute
+// the same hash, up to one hash per wave while the launch is small enough anyway (ped_quad_kernel).
+struct QuadShape {
+  int log_q, dup;
+  unsigned blocks;
 };
+static QuadShape quad_shape(size_t n, int nwin) {
+  QuadShape q{0, 0, 0};
+  for (int l = 3; l >= 1 && q.log_q == 0; --l) {
+    if (n <= quad_class_max(l, nwin)) q.log_q = l;
+  }
+  if (q.log_q == 0) return q;
+  while ((4 << (q.log_q + q.dup)) < 64 && ((n * 4) << (q.log_q + q.dup + 1)) <= 65536) ++q.dup;
+  if (g_quad_no_dup) q.dup = 0;  // A/B switch
+  q.blocks = (unsigned)((((n * 4) << (q.log_q + q.dup)) + 255) / 256);
+  return q;
+}
+// The one ladder from a run-time size class to the kernels' template arguments: launch(LOG_Q, SPARSE) is called
+// with integral constants.  The sparse forms exist for four and two quads only.
+template <class F>
+static void dispatch_quad(int log_q, bool sparse, F&& launch) {
+  using std::integral_constant;
+  if (sparse && log_q == 2) launch(integral_constant<int, 2>{}, std::true_type{});
+  else if (sparse) launch(integral_constant<int, 1>{}, std::true_type{});
+  else if (log_q == 3) launch(integral_constant<int, 3>{}, std::false_type{});
+  else if (log_q == 2) launch(integral_constant<int, 2>{}, std::false_type{});
+  else launch(integral_constant<int, 1>{}, std::false_type{});
+}
+
+// ---- host-side drivers -------------------------------------------------------------------------
 // Scratch is per stream, so independent calls issued on different HIP streams (e.g. several trees
 // in flight) never share X / ZZ / prefix planes.  Growing a buffer reallocates it: callers that
 // overlap streams should size the first call of each stream for their largest batch.
 static std::map<StreamKey, DeviceBuffer> g_stream_scratch;
-int get_scratch_public(size_t n, Scratch& s, hipStream_t st);
 static int get_scratch(size_t n, Scratch& s, hipStream_t st) { return get_scratch_public(n, s, st); }
 // The stream's scratch with `tail_bytes` more behind the flag (*tail, 256-byte aligned): the offsets, permutation
 // and status bytes of the ragged chains live there, in the same buffer and under the same rules.
@@ -1225,8 +1180,17 @@ void constant_window_counts(const PedPlan& p, int& cx, int& cy) {
     if (p.start[g] >= 252) ++cy;
   }
 }
-// The constant points of a sparse tree's levels (ped_partial_kernel): out[2 l], out[2 l + 1] for felts[l].
-// Returns SP_OK with *usable = false when the plan leaves no constant window on one of the sides.
+// Whether a gathered launch of class log_q takes the SPARSE kernels: nodes with one constant operand sum
+// 1 + nwin - cx (cy) points, and every quad still needs two of them.  Sets cx, cy.
+// (levels the eight-quad kernel takes - up to 2048 nodes, the top of an update where most nodes have two touched
+// children - stay with it: 21.5 us against 22.5 for the four-quad sparse form, timeline of quick_tree_update)
+static bool sparse_class(const PedPlan& plan, int log_q, int& cx, int& cy) {
+  if (!g_sparse_enabled || (log_q != 1 && log_q != 2)) return false;
+  constant_window_counts(plan, cx, cy);
+  const int shortest = 1 + plan.nwin - (cx > cy ? cx : cy);
+  return cx >= 1 && cy >= 1 && shortest >= (2 << log_q);
+}
+// The constant points of a sparse tree's levels (ped_partial_kernel): see pedersen.hpp.
 int enqueue_partial_points(const uint64_t* felts, int count, aff_packed* out, hipStream_t st, bool* usable) {
   Context& c = ctx();
   int cx, cy;
@@ -1242,7 +1206,6 @@ int enqueue_partial_points(const uint64_t* felts, int count, aff_packed* out, hi
 static int enqueue_pedersen_impl(const uint64_t* x, size_t xs, const uint64_t* y, size_t ys, uint64_t* out,
                                  size_t os, uint8_t* status, unsigned* flag, size_t n, hipStream_t st,
                                  const Scratch& s, const int2* src, const aff_packed* cpts);
-// Enqueue n hashes; x/y/out strides in felts.  `flag` (device, may be null) ORs item status.
 int enqueue_pedersen(const uint64_t* x, size_t xs, const uint64_t* y, size_t ys, uint64_t* out,
                      size_t os, uint8_t* status, unsigned* flag, size_t n, hipStream_t st,
                      const Scratch& s, const int2* src) {
@@ -1264,23 +1227,13 @@ int enqueue_pedersen_chain(const uint64_t* first, const uint64_t* words, long lo
   *done = false;
   Context& c = ctx();
   const int w0 = c.plan.bits[0], log2e = c.plan.log2e, nwin = c.plan.nwin;
-  if (!g_chain_fusion || !g_quad_enabled || nwin > 64 || n == 0 || steps < 2 || steps > 0x7fffffffull) return SP_OK;
-  int log_q = 0;  // the size classes of enqueue_pedersen_impl
-  if (n <= g_quad_max && nwin >= 16) log_q = 3;
-  else if (n <= 2 * g_quad_max && nwin >= 8) log_q = 2;
-  else if (n <= 4 * g_quad_max && nwin >= 4 && g_quad2_enabled) log_q = 1;
-  if (log_q == 0) return SP_OK;
-  int dup = 0;
-  while ((4 << (log_q + dup)) < 64 && ((n * 4) << (log_q + dup + 1)) <= 65536) ++dup;  // up to one hash per wave
-  if (g_quad_no_dup) dup = 0;
-  const unsigned blocks = (unsigned)((((n * 4) << (log_q + dup)) + 255) / 256);
-#define SP_LAUNCH_CHAIN(LOGQ)                                                                                      \
-  hipLaunchKernelGGL((ped_chain_kernel<LOGQ>), dim3(blocks), dim3(256), 0, st, first, words, word_stride, n, (int)steps, \
-                     h_right, c.ped, w0, log2e, nwin, flag, out, dup)
-  if (log_q == 3) SP_LAUNCH_CHAIN(3);
-  else if (log_q == 2) SP_LAUNCH_CHAIN(2);
-  else SP_LAUNCH_CHAIN(1);
-#undef SP_LAUNCH_CHAIN
+  if (!g_chain_fusion || n == 0 || steps < 2 || steps > 0x7fffffffull) return SP_OK;
+  const QuadShape q = quad_shape(n, nwin);
+  if (q.log_q == 0) return SP_OK;
+  dispatch_quad(q.log_q, false, [&](auto Q, auto) {
+    hipLaunchKernelGGL((ped_chain_kernel<decltype(Q)::value>), dim3(q.blocks), dim3(256), 0, st, first, words, word_stride,
+                       n, (int)steps, h_right, c.ped, w0, log2e, nwin, flag, out, q.dup);
+  });
   SP_HIP(hipGetLastError());
   *done = true;
   return SP_OK;
@@ -1309,33 +1262,15 @@ int enqueue_pedersen_path(uint64_t* felts, const uint64_t* emp, unsigned* flag, 
   *done = false;
   Context& c = ctx();
   const int w0 = c.plan.bits[0], log2e = c.plan.log2e, nwin = c.plan.nwin;
-  if (!g_path_fusion || !g_quad_enabled || nwin > 64 || n == 0 || pl.n_levels < 2) return SP_OK;
-  int log_q = 0;  // the size classes of enqueue_pedersen_impl
-  if (n <= g_quad_max && nwin >= 16) log_q = 3;
-  else if (n <= 2 * g_quad_max && nwin >= 8) log_q = 2;
-  else if (n <= 4 * g_quad_max && nwin >= 4 && g_quad2_enabled) log_q = 1;
-  if (log_q == 0) return SP_OK;
+  if (!g_path_fusion || n == 0 || pl.n_levels < 2) return SP_OK;
+  const QuadShape q = quad_shape(n, nwin);
+  if (q.log_q == 0) return SP_OK;
   int cx = 0, cy = 0;
-  bool sparse = false;
-  if (g_sparse_enabled && cpts_tree != nullptr && (log_q == 1 || log_q == 2)) {
-    constant_window_counts(c.plan, cx, cy);
-    const int shortest = 1 + nwin - (cx > cy ? cx : cy);
-    sparse = cx >= 1 && cy >= 1 && shortest >= (2 << log_q);
-  }
-  int dup = 0;
-  while ((4 << (log_q + dup)) < 64 && ((n * 4) << (log_q + dup + 1)) <= 65536) ++dup;  // up to one hash per wave
-  if (g_quad_no_dup) dup = 0;
-  const unsigned blocks = (unsigned)((((n * 4) << (log_q + dup)) + 255) / 256);
-#define SP_LAUNCH_PATH(LOGQ, SPARSEV)                                                                             \
-  hipLaunchKernelGGL((ped_path_kernel<LOGQ, SPARSEV>), dim3(blocks), dim3(256), 0, st, felts, emp, n, c.ped, w0, log2e, \
-                     nwin, flag, src_all, pl, dup, sparse ? cpts_tree : nullptr, cx, cy)
-  if (sparse) {
-    if (log_q == 2) SP_LAUNCH_PATH(2, true);
-    else SP_LAUNCH_PATH(1, true);
-  } else if (log_q == 3) SP_LAUNCH_PATH(3, false);
-  else if (log_q == 2) SP_LAUNCH_PATH(2, false);
-  else SP_LAUNCH_PATH(1, false);
-#undef SP_LAUNCH_PATH
+  const bool sparse = cpts_tree != nullptr && sparse_class(c.plan, q.log_q, cx, cy);
+  dispatch_quad(q.log_q, sparse, [&](auto Q, auto S) {
+    hipLaunchKernelGGL((ped_path_kernel<decltype(Q)::value, decltype(S)::value>), dim3(q.blocks), dim3(256), 0, st, felts,
+                       emp, n, c.ped, w0, log2e, nwin, flag, src_all, pl, q.dup, sparse ? cpts_tree : nullptr, cx, cy);
+  });
   SP_HIP(hipGetLastError());
   *done = true;
   return SP_OK;
@@ -1364,39 +1299,15 @@ static int enqueue_pedersen_impl(const uint64_t* x, size_t xs, const uint64_t* y
     else if (n * 2 <= g_split_lanes) log_l = 1;
     while (log_l > 0 && nwin < (2 << log_l)) --log_l;
   }
-  // quad-parallel latency kernels while the level fits one wave per SIMD: 8 quads per hash up to 2048
-  // hashes, 4 up to 4096 (same 18 rounds while nwin <= 20), 2 up to 8192
-  int log_q = 0;
-  if (g_quad_enabled && nwin <= 64) {
-    if (n <= g_quad_max && nwin >= 16) log_q = 3;
-    else if (n <= 2 * g_quad_max && nwin >= 8) log_q = 2;
-    else if (n <= 4 * g_quad_max && nwin >= 4 && g_quad2_enabled) log_q = 1;
-  }
-  // sparse level: nodes with one constant operand sum 1 + nwin - cx (cy) points
-  int cx = 0, cy = 0;
-  bool sparse = false;
-  // (levels the eight-quad kernel takes - up to 2048 nodes, the top of an update where most nodes have two touched
-  // children - stay with it: 21.5 us against 22.5 for the four-quad sparse form, gpurun timeline of quick_tree_update)
-  if (g_sparse_enabled && cpts != nullptr && src != nullptr && (log_q == 1 || log_q == 2)) {
-    constant_window_counts(c.plan, cx, cy);
-    const int shortest = 1 + nwin - (cx > cy ? cx : cy);
-    sparse = cx >= 1 && cy >= 1 && shortest >= (2 << log_q);
-  }
-  if (log_q != 0) {
-    int dup = 0;
-    while ((4 << (log_q + dup)) < 64 && ((n * 4) << (log_q + dup + 1)) <= 65536) ++dup;  // up to one hash per wave
-    if (g_quad_no_dup) dup = 0;  // A/B switch
-    const unsigned blocks = (unsigned)((((n * 4) << (log_q + dup)) + 255) / 256);
-#define SP_LAUNCH_QUAD(LOGQ, SPARSEV)                                                                           \
-  hipLaunchKernelGGL((ped_quad_kernel<LOGQ, SPARSEV>), dim3(blocks), dim3(256), 0, st, x, y, xs, ys, n, c.ped, w0, \
-                     log2e, nwin, status, flag, src, out, os, dup, cpts, cx, cy)
-    if (sparse) {
-      if (log_q == 2) SP_LAUNCH_QUAD(2, true);
-      else SP_LAUNCH_QUAD(1, true);
-    } else if (log_q == 3) SP_LAUNCH_QUAD(3, false);
-    else if (log_q == 2) SP_LAUNCH_QUAD(2, false);
-    else SP_LAUNCH_QUAD(1, false);
-#undef SP_LAUNCH_QUAD
+  // quad-parallel latency kernels while the level fits one wave per SIMD (quad_shape)
+  const QuadShape q = quad_shape(n, nwin);
+  if (q.log_q != 0) {
+    int cx = 0, cy = 0;
+    const bool sparse = cpts != nullptr && src != nullptr && sparse_class(c.plan, q.log_q, cx, cy);
+    dispatch_quad(q.log_q, sparse, [&](auto Q, auto S) {
+      hipLaunchKernelGGL((ped_quad_kernel<decltype(Q)::value, decltype(S)::value>), dim3(q.blocks), dim3(256), 0, st, x, y,
+                         xs, ys, n, c.ped, w0, log2e, nwin, status, flag, src, out, os, q.dup, cpts, cx, cy);
+    });
     fused = true;
   } else if (log_l == 0 && !(g_split_enabled && g_fuse_enabled && n <= 65536)) {
     // A launch takes ceil(waves / 1024) x the chain of one wave, so a level that is not a whole number of
@@ -1469,10 +1380,12 @@ static int enqueue_pedersen_impl(const uint64_t* x, size_t xs, const uint64_t* y
   return SP_OK;
 }
 
-// ---- chains of unequal length (sp_pedersen_chains_ragged[_dev]) ----------------------------------
-static bool g_chain_ragged = getenv("STARKPERP_NO_CHAIN_RAGGED") == nullptr;  // A/B switch
-// Host-side staging of a ragged call's offsets (and, in the fallback, its permutation and index pairs): page-locked,
-// one per stream, so that the caller's array is consumed before the call returns and the copy to the device is a
+// ---- ragged walks: chains of unequal length (sp_pedersen_chains_ragged[_dev], sp_state_batch) and Merkle paths
+// ---- (sp_merkle_fold_paths[_dev], sp_merkle_verify_paths) --------------------------------------------------
+static bool g_chain_ragged = getenv("STARKPERP_NO_CHAIN_RAGGED") == nullptr;  // A/B switch, both forms
+static bool g_path_fold = getenv("STARKPERP_NO_PATH_FOLD") == nullptr;        // A/B switch, the path form only
+// Host-side staging of a ragged call's offsets and keys (in the fallback: of its plan's metadata): page-locked,
+// one per stream, so that the caller's arrays are consumed before the call returns and the copy to the device is a
 // true asynchronous DMA.  The event marks the last copy out of the buffer: it is waited for before the buffer is
 // written again - the only wait of a ragged _dev call, and one for a copy that has long run when the next call comes.
 struct RaggedStage {
@@ -1488,121 +1401,103 @@ void release_ragged_stage() {
   }
   g_ragged_stage.clear();
 }
-// `bytes` of metadata at `meta` (host) -> d_meta, through the stream's page-locked buffer.
-static int ragged_stage_copy(const void* meta, size_t bytes, void* d_meta, hipStream_t st) {
+// The host arrays a (a_bytes) and b (b_bytes, may be 0), one behind the other -> d_meta, through the stream's
+// page-locked buffer.
+static int ragged_stage_copy(const void* a, size_t a_bytes, const void* b, size_t b_bytes, void* d_meta, hipStream_t st) {
   RaggedStage& rs = g_ragged_stage[stream_key(st)];
   if (rs.pending) {
     SP_HIP(hipEventSynchronize(rs.copied));
     rs.pending = false;
   }
   if (rs.copied == nullptr) SP_HIP(hipEventCreateWithFlags(&rs.copied, hipEventDisableTiming));
-  SP_HIP(rs.host.reserve(bytes));
-  std::memcpy(rs.host.ptr, meta, bytes);
-  SP_HIP(hipMemcpyAsync(d_meta, rs.host.ptr, bytes, hipMemcpyHostToDevice, st));
+  SP_HIP(rs.host.reserve(a_bytes + b_bytes));
+  if (a_bytes) std::memcpy(rs.host.ptr, a, a_bytes);
+  if (b_bytes) std::memcpy((char*)rs.host.ptr + a_bytes, b, b_bytes);
+  SP_HIP(hipMemcpyAsync(d_meta, rs.host.ptr, a_bytes + b_bytes, hipMemcpyHostToDevice, st));
   SP_HIP(hipEventRecord(rs.copied, st));
   rs.pending = true;
   return SP_OK;
 }
 // Largest batch one ragged launch takes under the current window plan and switches: the top of the size classes
-// of enqueue_pedersen_chain (0: no fused kernel - the per-step fallback serves the call).
+// (0: no fused kernel - the per-step fallback serves the call).
 static size_t chain_ragged_cap() {
+  if (!g_chain_ragged) return 0;
   const int nwin = ctx().plan.nwin;
-  if (!g_chain_ragged || !g_quad_enabled || nwin > 64) return 0;
-  if (nwin >= 4 && g_quad2_enabled) return 4 * g_quad_max;
-  if (nwin >= 8) return 2 * g_quad_max;
-  if (nwin >= 16) return g_quad_max;
-  return 0;
+  return std::max({quad_class_max(1, nwin), quad_class_max(2, nwin), quad_class_max(3, nwin)});
 }
-// n chains, chain i = felts off[i] .. off[i + 1) of `elems` (device), `off` = n + 1 validated HOST offsets; out and
-// status (n bytes or null) on the device.  Enqueues on `st` and returns; the caller holds the context lock.
-// Fused: consecutive slices of at most chain_ragged_cap() chains, one ped_chain_ragged_kernel launch each.
-// Fallback: the chains sorted by falling length (a permutation), so that the chains still running at step j are a
-// prefix; step j is one enqueue_pedersen launch over that prefix in gathered mode - the running hashes and a copy
-// of the words share one work buffer, the index pairs address it - and a last launch puts hashes and status bytes
-// back in the caller's order.
-int enqueue_pedersen_chain_ragged(const uint64_t* elems, const uint32_t* off, size_t n, uint64_t* out, uint8_t* status,
-                                  hipStream_t st) {
+// See pedersen.hpp for the arguments.
+// Fused: consecutive slices of at most chain_ragged_cap() walks, one ped_fold_ragged_kernel launch each; the offsets
+// (behind the keys, for paths) go over in one copy.
+// Fallback (ragged_plan.hpp): the walks sorted by falling length, step s one enqueue_pedersen launch in gathered mode
+// over the prefix still running - the running values and a copy of the caller's felts share one work buffer, the
+// index pairs address it - and a last launch that restores the caller's order.
+int enqueue_pedersen_fold_ragged(const uint64_t* leaves, const uint64_t* words, const uint32_t* off, const uint64_t* keys,
+                                 size_t n, uint64_t* out, uint8_t* status, const uint64_t* expect, size_t estride,
+                                 uint8_t* verdict, hipStream_t st) {
   if (n == 0) return SP_OK;
   Context& c = ctx();
   const int w0 = c.plan.bits[0], log2e = c.plan.log2e, nwin = c.plan.nwin;
+  const bool sided = keys != nullptr;
   const size_t total = off[n];
-  const size_t cap = chain_ragged_cap();
+  const size_t cap = sided && !g_path_fold ? 0 : chain_ragged_cap();
   Scratch s;
   char* tail = nullptr;
   if (cap != 0) {
-    int rc = get_scratch_tail(1, (n + 1) * sizeof(uint32_t), s, &tail, st);
+    // metadata, one copy: keys[n] (64-bit, paths only) | off[n + 1]
+    const size_t key_bytes = sided ? n * sizeof(uint64_t) : 0, off_bytes = (n + 1) * sizeof(uint32_t);
+    int rc = get_scratch_tail(1, key_bytes + off_bytes, s, &tail, st);
     if (rc != SP_OK) return rc;
     SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
-    uint32_t* d_off = (uint32_t*)tail;
-    rc = ragged_stage_copy(off, (n + 1) * sizeof(uint32_t), d_off, st);
+    const uint64_t* d_keys = (const uint64_t*)tail;
+    const uint32_t* d_off = (const uint32_t*)(tail + key_bytes);
+    rc = ragged_stage_copy(keys, key_bytes, off, off_bytes, tail, st);
     if (rc != SP_OK) return rc;
     for (size_t b = 0; b < n; b += cap) {
       const size_t m = n - b < cap ? n - b : cap;
-      int log_q = 1;  // the size classes of enqueue_pedersen_chain; m <= cap always has one
-      if (m <= g_quad_max && nwin >= 16) log_q = 3;
-      else if (m <= 2 * g_quad_max && nwin >= 8) log_q = 2;
-      int dup = 0;
-      while ((4 << (log_q + dup)) < 64 && ((m * 4) << (log_q + dup + 1)) <= 65536) ++dup;  // up to one chain per wave
-      if (g_quad_no_dup) dup = 0;
-      const unsigned blocks = (unsigned)((((m * 4) << (log_q + dup)) + 255) / 256);
-#define SP_LAUNCH_RAGGED(LOGQ)                                                                                       \
-  hipLaunchKernelGGL((ped_chain_ragged_kernel<LOGQ>), dim3(blocks), dim3(256), 0, st, elems, d_off + b, m, c.ped, w0, \
-                     log2e, nwin, s.flag, status ? status + b : nullptr, out + 4 * b, dup)
-      if (log_q == 3) SP_LAUNCH_RAGGED(3);
-      else if (log_q == 2) SP_LAUNCH_RAGGED(2);
-      else SP_LAUNCH_RAGGED(1);
-#undef SP_LAUNCH_RAGGED
+      const QuadShape q = quad_shape(m, nwin);  // m <= cap always has a size class
+      // the slice's offsets stay absolute (d_off + b), so `words` is not advanced
+      dispatch_quad(q.log_q, false, [&](auto Q, auto) {
+        if (sided)
+          hipLaunchKernelGGL((ped_fold_ragged_kernel<decltype(Q)::value, true>), dim3(q.blocks), dim3(256), 0, st,
+                             leaves + 4 * b, words, d_off + b, d_keys + b, m, c.ped, w0, log2e, nwin, s.flag,
+                             status ? status + b : nullptr, out + 4 * b, expect ? expect + 4 * b * estride : nullptr,
+                             estride, verdict ? verdict + b : nullptr, q.dup);
+        else
+          hipLaunchKernelGGL((ped_fold_ragged_kernel<decltype(Q)::value, false>), dim3(q.blocks), dim3(256), 0, st,
+                             nullptr, words, d_off + b, nullptr, m, c.ped, w0, log2e, nwin, s.flag,
+                             status ? status + b : nullptr, out + 4 * b, nullptr, 0, nullptr, q.dup);
+      });
       SP_HIP(hipGetLastError());
     }
     return SP_OK;
   }
   // ---- fallback ----
-  if (n + total > 0x7fffffffull) { set_error("ragged chains: more than 2^31 felts"); return SP_ERR_BAD_ARGUMENT; }
-  std::vector<uint32_t> perm(n);
-  for (size_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
-  std::stable_sort(perm.begin(), perm.end(),
-                   [&](uint32_t a, uint32_t b) { return off[a + 1] - off[a] > off[b + 1] - off[b]; });
-  const size_t maxlen = off[perm[0] + 1] - off[perm[0]];
-  const size_t n_pairs = total - n;  // sum over the steps of the chains still running = all hashes of the call
-  // metadata, one copy: off[n + 1] | perm[n] | step_off[maxlen] | index pairs (2 x n_pairs)
-  std::vector<uint32_t> meta(n + 1 + n + maxlen + 2 * n_pairs);
-  std::memcpy(meta.data(), off, (n + 1) * sizeof(uint32_t));
-  std::memcpy(meta.data() + n + 1, perm.data(), n * sizeof(uint32_t));
-  uint32_t* step_off = meta.data() + 2 * n + 1;
-  uint32_t* pairs = step_off + maxlen;
-  std::vector<size_t> running(maxlen, 0);  // running[j] = chains longer than j words
-  size_t m = n, pos = 0;
-  for (size_t j = 1; j < maxlen; ++j) {
-    while (m > 0 && off[perm[m - 1] + 1] - off[perm[m - 1]] <= j) --m;
-    running[j] = m;
-    step_off[j] = (uint32_t)pos;
-    for (size_t k = 0; k < m; ++k) {
-      const uint32_t o = (uint32_t)n + off[perm[k]];
-      pairs[2 * (pos + k)] = j == 1 ? o : (uint32_t)k;  // left: the chain's first word, later its running hash
-      pairs[2 * (pos + k) + 1] = o + (uint32_t)j;       // right: word j of the chain
-    }
-    pos += m;
+  if (ragged_work_felts(off, n, sided) > 0x7fffffffull) {
+    set_error(sided ? "merkle paths: more than 2^31 felts" : "ragged chains: more than 2^31 felts");
+    return SP_ERR_BAD_ARGUMENT;
   }
-  if (maxlen > 0) step_off[0] = 0;
-  const size_t meta_bytes = (meta.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
-  const size_t stat_bytes = (n_pairs + 255) & ~(size_t)255;
-  int rc = get_scratch_tail(n, meta_bytes + stat_bytes + (n + total) * 32, s, &tail, st);
+  const RaggedPlan p = ragged_plan(off, keys, n);
+  const size_t meta_bytes = (p.meta.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
+  const size_t stat_bytes = (p.n_pairs + 255) & ~(size_t)255;
+  int rc = get_scratch_tail(n, meta_bytes + stat_bytes + p.work_felts * 32, s, &tail, st);
   if (rc != SP_OK) return rc;
   SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
   uint32_t* d_meta = (uint32_t*)tail;
   uint8_t* d_stat = (uint8_t*)(tail + meta_bytes);
   uint64_t* d_work = (uint64_t*)(tail + meta_bytes + stat_bytes);
-  rc = ragged_stage_copy(meta.data(), meta.size() * sizeof(uint32_t), d_meta, st);
+  rc = ragged_stage_copy(p.meta.data(), p.meta.size() * sizeof(uint32_t), nullptr, 0, d_meta, st);
   if (rc != SP_OK) return rc;
-  SP_HIP(hipMemcpyAsync(d_work + 4 * n, elems, total * 32, hipMemcpyDeviceToDevice, st));
-  const int2* d_pairs = reinterpret_cast<const int2*>(d_meta + 2 * n + 1 + maxlen);
-  for (size_t j = 1; j < maxlen; ++j) {
-    rc = enqueue_pedersen(d_work, 1, d_work, 1, d_work, 1, d_stat + step_off[j], s.flag, running[j], st, s,
-                          d_pairs + step_off[j]);
+  if (sided) SP_HIP(hipMemcpyAsync(d_work + 4 * n, leaves, n * 32, hipMemcpyDeviceToDevice, st));
+  if (total > 0) SP_HIP(hipMemcpyAsync(d_work + 4 * (p.work_felts - total), words, total * 32, hipMemcpyDeviceToDevice, st));
+  const int2* d_pairs = reinterpret_cast<const int2*>(d_meta + p.pairs_at);
+  for (size_t j = 0; j < p.max_steps; ++j) {
+    rc = enqueue_pedersen(d_work, 1, d_work, 1, d_work, 1, d_stat + p.step_off()[j], s.flag, p.running[j], st, s,
+                          d_pairs + p.step_off()[j]);
     if (rc != SP_OK) return rc;
   }
-  hipLaunchKernelGGL(ped_chain_ragged_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_work, elems,
-                     d_meta, d_meta + n + 1, d_meta + 2 * n + 1, d_stat, n, s.flag, status, out);
+  hipLaunchKernelGGL(ped_fold_ragged_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_work,
+                     sided ? leaves : words, sided, d_meta, d_meta + n + 1, d_meta + 2 * n + 1, d_stat, n, s.flag, status, out,
+                     expect, estride, verdict);
   SP_HIP(hipGetLastError());
   return SP_OK;
 }
@@ -1615,114 +1510,6 @@ static bool ragged_offsets_ok(const uint32_t* off, size_t n) {
   return true;
 }
 
-// ---- Merkle paths (sp_merkle_fold_paths[_dev], sp_merkle_verify_paths) ----------------------------
-static bool g_path_fold = getenv("STARKPERP_NO_PATH_FOLD") == nullptr;  // A/B switch
-// n paths: path i starts from leaves + 4 i and takes the siblings off[i] .. off[i + 1) of `siblings` (device), bit j
-// of keys[i] = the side at step j; `off` (n + 1) and `keys` (n) are validated HOST arrays.  roots, status (n bytes or
-// null), expect (+ 4 i estride, estride 0 or 1) and verdict (n bytes; both or neither) on the device.  Enqueues on
-// `st` and returns; the caller holds the context lock.
-// Fused: consecutive slices of at most chain_ragged_cap() paths, one ped_path_fold_kernel launch each; keys and
-// offsets go over in one copy.  Fallback: as enqueue_pedersen_chain_ragged - the paths sorted by falling length, step
-// j one gathered enqueue_pedersen launch over the prefix still running, the index pair of a path swapped where its
-// side bit of that step is set - and a last launch that restores the caller's order.
-int enqueue_pedersen_path_fold(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, const uint64_t* keys,
-                               size_t n, uint64_t* roots, uint8_t* status, const uint64_t* expect, size_t estride,
-                               uint8_t* verdict, hipStream_t st) {
-  if (n == 0) return SP_OK;
-  Context& c = ctx();
-  const int w0 = c.plan.bits[0], log2e = c.plan.log2e, nwin = c.plan.nwin;
-  const size_t total = off[n];
-  const size_t cap = g_path_fold ? chain_ragged_cap() : 0;
-  Scratch s;
-  char* tail = nullptr;
-  if (cap != 0) {
-    // metadata, one copy: keys[n] (64-bit) | off[n + 1]
-    std::vector<uint64_t> meta(n + (n + 2) / 2);
-    std::memcpy(meta.data(), keys, n * sizeof(uint64_t));
-    std::memcpy(meta.data() + n, off, (n + 1) * sizeof(uint32_t));
-    int rc = get_scratch_tail(1, meta.size() * sizeof(uint64_t), s, &tail, st);
-    if (rc != SP_OK) return rc;
-    SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
-    const uint64_t* d_keys = (const uint64_t*)tail;
-    const uint32_t* d_off = (const uint32_t*)(d_keys + n);
-    rc = ragged_stage_copy(meta.data(), meta.size() * sizeof(uint64_t), tail, st);
-    if (rc != SP_OK) return rc;
-    for (size_t b = 0; b < n; b += cap) {
-      const size_t m = n - b < cap ? n - b : cap;
-      int log_q = 1;  // the size classes of enqueue_pedersen_chain; m <= cap always has one
-      if (m <= g_quad_max && nwin >= 16) log_q = 3;
-      else if (m <= 2 * g_quad_max && nwin >= 8) log_q = 2;
-      int dup = 0;
-      while ((4 << (log_q + dup)) < 64 && ((m * 4) << (log_q + dup + 1)) <= 65536) ++dup;  // up to one path per wave
-      if (g_quad_no_dup) dup = 0;
-      const unsigned blocks = (unsigned)((((m * 4) << (log_q + dup)) + 255) / 256);
-      // the slice's offsets stay absolute (d_off + b), so `siblings` is not advanced
-#define SP_LAUNCH_FOLD(LOGQ)                                                                                          \
-  hipLaunchKernelGGL((ped_path_fold_kernel<LOGQ>), dim3(blocks), dim3(256), 0, st, leaves + 4 * b, siblings, d_off + b, \
-                     d_keys + b, m, c.ped, w0, log2e, nwin, s.flag, status ? status + b : nullptr, roots + 4 * b,       \
-                     expect ? expect + 4 * b * estride : nullptr, estride, verdict ? verdict + b : nullptr, dup)
-      if (log_q == 3) SP_LAUNCH_FOLD(3);
-      else if (log_q == 2) SP_LAUNCH_FOLD(2);
-      else SP_LAUNCH_FOLD(1);
-#undef SP_LAUNCH_FOLD
-      SP_HIP(hipGetLastError());
-    }
-    return SP_OK;
-  }
-  // ---- fallback ----
-  if (2 * n + total > 0x7fffffffull) { set_error("merkle paths: more than 2^31 felts"); return SP_ERR_BAD_ARGUMENT; }
-  std::vector<uint32_t> perm(n);
-  for (size_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
-  std::stable_sort(perm.begin(), perm.end(),
-                   [&](uint32_t a, uint32_t b) { return off[a + 1] - off[a] > off[b + 1] - off[b]; });
-  const size_t maxlen = off[perm[0] + 1] - off[perm[0]];
-  const size_t n_pairs = total;  // sum over the steps of the paths still running = all hashes of the call
-  // metadata, one copy: off[n + 1] | perm[n] | step_off[maxlen] | (pad to 8 bytes) | index pairs (2 x n_pairs)
-  const size_t pairs_at = (2 * n + 1 + maxlen + 1) & ~(size_t)1;
-  std::vector<uint32_t> meta(pairs_at + 2 * n_pairs);
-  std::memcpy(meta.data(), off, (n + 1) * sizeof(uint32_t));
-  std::memcpy(meta.data() + n + 1, perm.data(), n * sizeof(uint32_t));
-  uint32_t* step_off = meta.data() + 2 * n + 1;
-  uint32_t* pairs = meta.data() + pairs_at;
-  std::vector<size_t> running(maxlen, 0);  // running[j] = paths of more than j siblings
-  size_t m = n, pos = 0;
-  // work buffer: running nodes [0, n) in sorted order | the leaves [n, 2 n) | the siblings [2 n, 2 n + total)
-  for (size_t j = 0; j < maxlen; ++j) {
-    while (m > 0 && off[perm[m - 1] + 1] - off[perm[m - 1]] <= j) --m;
-    running[j] = m;
-    step_off[j] = (uint32_t)pos;
-    for (size_t k = 0; k < m; ++k) {
-      const uint32_t h = j == 0 ? (uint32_t)n + perm[k] : (uint32_t)k;    // the leaf, later the running node
-      const uint32_t w = 2 * (uint32_t)n + off[perm[k]] + (uint32_t)j;    // sibling j of the path
-      const bool right = ((keys[perm[k]] >> j) & 1) != 0;
-      pairs[2 * (pos + k)] = right ? w : h;
-      pairs[2 * (pos + k) + 1] = right ? h : w;
-    }
-    pos += m;
-  }
-  const size_t meta_bytes = (meta.size() * sizeof(uint32_t) + 255) & ~(size_t)255;
-  const size_t stat_bytes = (n_pairs + 255) & ~(size_t)255;
-  int rc = get_scratch_tail(n, meta_bytes + stat_bytes + (2 * n + total) * 32, s, &tail, st);
-  if (rc != SP_OK) return rc;
-  SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
-  uint32_t* d_meta = (uint32_t*)tail;
-  uint8_t* d_stat = (uint8_t*)(tail + meta_bytes);
-  uint64_t* d_work = (uint64_t*)(tail + meta_bytes + stat_bytes);
-  rc = ragged_stage_copy(meta.data(), meta.size() * sizeof(uint32_t), d_meta, st);
-  if (rc != SP_OK) return rc;
-  SP_HIP(hipMemcpyAsync(d_work + 4 * n, leaves, n * 32, hipMemcpyDeviceToDevice, st));
-  if (total > 0) SP_HIP(hipMemcpyAsync(d_work + 8 * n, siblings, total * 32, hipMemcpyDeviceToDevice, st));
-  const int2* d_pairs = reinterpret_cast<const int2*>(d_meta + pairs_at);
-  for (size_t j = 0; j < maxlen; ++j) {
-    rc = enqueue_pedersen(d_work, 1, d_work, 1, d_work, 1, d_stat + step_off[j], s.flag, running[j], st, s,
-                          d_pairs + step_off[j]);
-    if (rc != SP_OK) return rc;
-  }
-  hipLaunchKernelGGL(ped_path_fold_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_work, leaves,
-                     d_meta, d_meta + n + 1, d_meta + 2 * n + 1, d_stat, n, s.flag, status, roots, expect, estride, verdict);
-  SP_HIP(hipGetLastError());
-  return SP_OK;
-}
 // Validates a path call's arguments and returns the offsets to use: `off` itself, or (off == NULL) the uniform
 // offsets i * height built in `uniform`.  nullptr: a bad argument, the text is in sp_last_error.
 static const uint32_t* path_offsets_ok(const uint32_t* off, unsigned height, const uint64_t* keys, size_t n,
@@ -1779,8 +1566,8 @@ static int merkle_paths_host(const uint64_t* leaves, const uint64_t* siblings, c
   int rc;
   {
     ctx_lock lk(ctx().mu);
-    rc = enqueue_pedersen_path_fold(d_leaves, d_sib, off, keys, n, d_roots, d_st, verify ? d_exp : nullptr,
-                                    n_expected == n ? 1 : 0, verify ? d_ver : nullptr, L.stream);
+    rc = enqueue_pedersen_fold_ragged(d_leaves, d_sib, off, keys, n, d_roots, d_st, verify ? d_exp : nullptr,
+                                      n_expected == n ? 1 : 0, verify ? d_ver : nullptr, L.stream);
   }
   if (rc != SP_OK) return rc;
   if (verify) {
@@ -1967,7 +1754,7 @@ int sp_pedersen_chains(const uint64_t* elems, size_t width, size_t depth, uint64
   return SP_OK;
 }
 
-// Chains of unequal length in one call (ped_chain_ragged_kernel): chain i = the felts off[i] .. off[i + 1) of
+// Chains of unequal length in one call (ped_fold_ragged_kernel, chain form): chain i = the felts off[i] .. off[i + 1) of
 // elems.  Enqueues and returns; the HOST array `off` has been copied when it does.
 int sp_pedersen_chains_ragged_dev(const uint64_t* elems, const uint32_t* off, size_t n, uint64_t* out, uint8_t* status,
                                   void* stream) {
@@ -2014,7 +1801,7 @@ int sp_pedersen_chains_ragged(const uint64_t* elems, const uint32_t* off, size_t
   return SP_OK;
 }
 
-// Merkle paths folded in one launch (ped_path_fold_kernel): path i starts from leaves[i], bit l of keys[i] is the side
+// Merkle paths folded in one launch (ped_fold_ragged_kernel, path form): path i starts from leaves[i], bit l of keys[i] is the side
 // at level l.  Enqueues and returns; the HOST arrays `off` and `keys` have been copied when it does.
 int sp_merkle_fold_paths_dev(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, unsigned height,
                              const uint64_t* keys, size_t n, uint64_t* roots, uint8_t* status, void* stream) {
@@ -2025,7 +1812,7 @@ int sp_merkle_fold_paths_dev(const uint64_t* leaves, const uint64_t* siblings, c
   off = path_offsets_ok(off, height, keys, n, uniform);
   if (off == nullptr) return SP_ERR_BAD_ARGUMENT;
   ctx_lock lk(ctx().mu);
-  return enqueue_pedersen_path_fold(leaves, siblings, off, keys, n, roots, status, nullptr, 0, nullptr, (hipStream_t)stream);
+  return enqueue_pedersen_fold_ragged(leaves, siblings, off, keys, n, roots, status, nullptr, 0, nullptr, (hipStream_t)stream);
 }
 
 // Host-pointer variants: one staged round trip on a host lane; the verifier compares on the device and brings back

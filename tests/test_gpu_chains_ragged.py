@@ -1,6 +1,7 @@
-"""GPU parity of the ragged hash chains (sp_pedersen_chains_ragged[_dev], ped_chain_ragged_kernel): chains of
-unequal length in one launch against the C oracle, the reference-pinned rows that now take this path, per-chain
-status, bad arguments, the _dev variant and the per-step fallback."""
+"""GPU parity of the ragged hash chains (sp_pedersen_chains_ragged[_dev], the chain form of ped_fold_ragged_kernel):
+chains of unequal length in one launch against the C oracle, the reference-pinned rows that now take this path,
+per-chain status, bad arguments, the _dev variant, the per-step fallback, and the same data through the path form of
+the kernel (sp_merkle_fold_paths)."""
 import ctypes
 import json
 import os
@@ -66,6 +67,20 @@ LENGTH_PATTERNS = {
 def test_length_patterns_vs_c_oracle(batch, name):
     chains = cases.random_chains(LENGTH_PATTERNS[name], seed=len(name))
     assert batch.pedersen_chains_ragged(chains) == cases.oracle_fold(chains)
+
+
+def test_chains_and_paths_fold_the_same_data(batch_np):
+    """A chain is a path with key 0 whose leaf is the chain's first word and whose siblings are the rest: the two
+    forms of the one kernel give the same values and status bytes, and both are the oracle's."""
+    chains = cases.random_chains([1, 2, 3, 7, 1, 2, 3, 7, 1], seed=77)
+    words, off = cases.csr(chains)
+    got_c, st_c = batch_np.pedersen_chains_ragged(words, off)
+    leaves = batch_np.felts_from_ints([c[0] for c in chains])
+    sib = batch_np.felts_from_ints([w for c in chains for w in c[1:]])
+    sib_off = np.array([0] + list(np.cumsum([len(c) - 1 for c in chains])), dtype=np.uint32)
+    got_p, st_p = batch_np.merkle_fold_paths(leaves, sib, np.zeros(len(chains), dtype=np.uint64), offsets=sib_off)
+    assert (got_c == got_p).all() and (st_c == st_p).all() and not st_c.any()
+    assert batch_np.ints_from_felts(got_c) == cases.oracle_fold(chains)
 
 
 class CountingLib:

@@ -1,5 +1,5 @@
-"""GPU parity of the Merkle path calls (sp_merkle_fold_paths[_dev], sp_merkle_verify_paths, ped_path_fold_kernel and
-its per-step fallback) against the C oracle: size classes and slice edges, side bits, ragged lengths inside one block,
+"""GPU parity of the Merkle path calls (sp_merkle_fold_paths[_dev], sp_merkle_verify_paths, the path form of
+ped_fold_ragged_kernel and its per-step fallback) against the C oracle: size classes and slice edges, side bits, ragged lengths inside one block,
 the sp_tree_prove round trip, per-item verdicts and status, bad arguments, the fallback switches in a child process,
 both window plans, the prover's Merkle openings and a plain-C consumer."""
 import copy

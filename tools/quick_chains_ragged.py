@@ -2,7 +2,7 @@
 """Message hashes of a mixed transaction batch, host-inclusive, three ways in one process (through starkperp.batch_np:
 no Python-int packing in the timing): 4096 items - 70 % limit orders and 20 % transfers (5 words), 5 % conditional
 transfers (6 words), 5 % withdrawals to an address (3 words), interleaved - plus 32 oracle prices (2 words).
-  (a) one sp_pedersen_chains_ragged call (ped_chain_ragged_kernel);
+  (a) one sp_pedersen_chains_ragged call (ped_fold_ragged_kernel, chain form);
   (b) the way before it: one pedersen_chains call per length class plus pedersen_hash_many for the 2-word items;
   (c) the floor: pedersen_chains on 4128 chains that all have the deepest length (6).
 Median of the calls after a warm-up; prints a / b and a / c.
