@@ -23,7 +23,7 @@
  *     serialises the host-side bookkeeping; scratch, window tables of the verifier and NTT work
  *     columns are per stream, so _dev calls on different streams overlap on the device.  The
  *     host-pointer batches that carry no shared state - sp_pedersen_batch, sp_pedersen_chains,
- *     sp_pedersen_chains_ragged, sp_merkle_fold_paths, sp_merkle_verify_paths,
+ *     sp_pedersen_chains_ragged, sp_merkle_fold_paths, sp_merkle_verify_paths, sp_merkle_verify_update,
  *     sp_ecdsa_verify_batch (per-signature ladder), sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch,
  *     sp_public_key_batch -
  *     run on one of 16 host lanes (own stream, own staging buffer) and hold the lock only while a
@@ -256,6 +256,51 @@ int sp_merkle_fold_paths(const uint64_t* leaves, const uint64_t* siblings, const
 int sp_merkle_verify_paths(const uint64_t* leaves, const uint64_t* siblings, const uint32_t* off, unsigned height,
                            const uint64_t* keys, size_t n, const uint64_t* expected, size_t n_expected,
                            uint8_t* verdict, uint8_t* status);
+/* Verifying a multi-update from its witnesses: the statement of merkle_multi_update(prev_leaves, new_leaves, height,
+ * prev_root, new_root) (state/state.cairo:155-173, the walk of starkware/python/merkle_tree.py:4-26 through
+ * program_input['merkle_facts'], main.cairo:39-40, 61-64) checked against the records sp_tree_witness exports, without a
+ * tree handle.  A record carries its node and both children, so no check waits for another: every record is hashed
+ * once, all of them in ONE bulk launch sequence, and the rest is comparisons of felts (witness_check_kernel).
+ *   keys          n HOST words, strictly increasing, < 2^height, 1 <= height <= 64 (in both calls, like the two roots)
+ *   prev_leaves, new_leaves   n felts each: the leaf at keys[j] before and after the update
+ *   n_records     must equal sp_tree_witness_size(height, keys, n) = R
+ *   node, left, right   2 R felts each: the R records of the witness taken BEFORE the update, then the R records taken
+ *                 AFTER it, both in sp_tree_witness's order (level 1 .. height, ascending index inside a level): two
+ *                 sp_tree_witness outputs, one behind the other.  The POSITION of a record is never taken from the
+ *                 caller: it follows from the keys alone, so a witness cannot claim one.
+ *   status        2 R bytes (before half, then after half) or NULL; byte u is the OR of
+ *                   SP_HASH_OUT_OF_RANGE, SP_HASH_UNHASHABLE   from hashing left[u], right[u] (a felt >= p is no bad
+ *                                                 argument: it is SP_HASH_OUT_OF_RANGE on its record)
+ *                   SP_WITNESS_HASH_MISMATCH      the status of the hash is 0 and H(left[u], right[u]) != node[u]
+ *                   SP_WITNESS_LINK_MISMATCH      a child that lies on a key's path is not the node of the record at
+ *                                                 (level - 1, 2 index + c) of the same half; at level 1 it is compared
+ *                                                 with prev_leaves[j] / new_leaves[j] of that key
+ *                   SP_WITNESS_SIBLING_CHANGED    a child on NO key's path differs between the before and the after
+ *                                                 record of this position (set on both halves): the untouched side of
+ *                                                 the tree must be the same node in the old and in the new tree
+ *                   SP_WITNESS_ROOT_MISMATCH      last record of a half only: its node is not prev_root / new_root
+ *   *verdict      SP_PATH_TRUE iff every one of the 2 R status bytes is 0, reduced on the device (it is preset and
+ *                 cleared by one atomic per wave on the aligned 32-bit word that holds the byte)
+ * n == 0: SP_OK, *verdict = (prev_root == new_root); n_records must be 0 and nothing else is read.
+ * SP_ERR_BAD_ARGUMENT, with nothing written: keys not strictly increasing or out of range, a height outside 1 .. 64,
+ * n_records != R, 2 R >= 2^31, a null pointer (status excepted).
+ * The host call runs on a host lane like the other stateless host-pointer batches: it holds the library lock only to
+ * enqueue, stages its inputs through page-locked memory up to 4 MiB and copies directly above that, and brings back
+ * one byte (plus the 2 R status bytes when asked for).  The _dev call takes the felt arrays, status and verdict on the
+ * device, keys and the two roots on the host; it enqueues on `stream` and returns once it has consumed keys and roots.
+ * Cost: DESIGN.md 4.7, tools/quick_verify_update.py, profiles/verify_update.txt. */
+#define SP_WITNESS_HASH_MISMATCH 0x04
+#define SP_WITNESS_LINK_MISMATCH 0x08
+#define SP_WITNESS_SIBLING_CHANGED 0x20
+#define SP_WITNESS_ROOT_MISMATCH 0x40
+int sp_merkle_verify_update_dev(unsigned height, const uint64_t* keys, size_t n, const uint64_t* prev_leaves,
+                                const uint64_t* new_leaves, const uint64_t* prev_root, const uint64_t* new_root,
+                                const uint64_t* node, const uint64_t* left, const uint64_t* right, size_t n_records,
+                                uint8_t* verdict, uint8_t* status, void* stream);
+int sp_merkle_verify_update(unsigned height, const uint64_t* keys, size_t n, const uint64_t* prev_leaves,
+                            const uint64_t* new_leaves, const uint64_t* prev_root, const uint64_t* new_root,
+                            const uint64_t* node, const uint64_t* left, const uint64_t* right, size_t n_records,
+                            uint8_t* verdict, uint8_t* status);
 /* Threading of the sp_tree_* calls: a tree has its own HIP stream, work buffer and mutex.  An operation holds
  * the tree's mutex from start to end and the library lock only while it enqueues; the device work of an update
  * (the level launches) runs without the library lock, so other trees and the stateless batches go on meanwhile. */

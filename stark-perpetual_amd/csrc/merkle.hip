@@ -28,9 +28,31 @@ namespace sp {
 static DeviceBuffer g_sparse_buf;
 // empty-subtree roots are a pure function of the empty leaf: cached on the host per leaf value
 static std::map<std::vector<uint64_t>, std::vector<uint64_t>> g_empty_cache;  // leaf -> 65 felts
+// Work buffer of sp_merkle_verify_update[_dev], one per stream like the hash scratch: roots | node indices | child lists
+// | hashes | their status bytes.  It grows the way a tree's slot table does (tree_reserve): the old allocation is
+// RETIRED, not freed - hipFree waits for the whole device - and goes back at the next growth, behind a wait for the
+// stream alone.  `host` stages keys and roots (page-locked, so a _dev call has consumed both when it returns); `copied`
+// marks the last copy out of it and is waited for before it is written again (RaggedStage of pedersen.hip).
+struct VerifyWork {
+  void* ptr = nullptr;
+  void* retired = nullptr;
+  size_t bytes = 0;
+  PinnedBuffer host;
+  hipEvent_t copied = nullptr;
+  bool pending = false;
+};
+static std::map<StreamKey, VerifyWork> g_verify_work;
 void release_merkle_state() {
   g_sparse_buf.release();
   g_empty_cache.clear();
+  for (auto& kv : g_verify_work) {
+    VerifyWork& w = kv.second;
+    if (w.ptr) (void)hipFree(w.ptr);
+    if (w.retired) (void)hipFree(w.retired);
+    if (w.copied) (void)hipEventDestroy(w.copied);
+    w.host.release();
+  }
+  g_verify_work.clear();
 }
 
 }  // namespace sp
@@ -410,6 +432,73 @@ tree_prove_kernel(const TreeSlot* __restrict__ tab, uint64_t mask, const uint64_
     if (!v) v = emp;
 #pragma unroll
     for (int w = 0; w < 4; ++w) leaves[4 * (size_t)j + w] = v[w];
+  }
+}
+// ---- verifying a multi-update from its witnesses (sp_merkle_verify_update): nothing is looked up, nothing hashed ----
+__device__ __forceinline__ bool felt_same(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b) {
+  const u256 x = ld_u256(a), y = ld_u256(b);  // two 16-byte loads each
+  uint32_t d = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) d |= x.w[i] ^ y.w[i];
+  return d == 0;
+}
+// One thread per POSITION u of the keys' induced subtree (the order of the records, see tree_witness_kernel); it takes
+// the before record (u) and the after record (n_records + u) of its position together.  src_all is what
+// tree_children_kernel wrote for the keys: the parents' running count is the record number, so src_all[u] is the
+// child list of position u - per side the place of the child among the values of level - 1 (val_base + j: leaf j at
+// level 1, else record idx_off[level - 1] - cnt[0] + j), or TREE_PENDING = that child is on no key's path.  Per half:
+// `hashed` (one bulk launch sequence over left, right of all 2 R records) against node where the hash has status 0; a
+// child on a path against the node of the child record of the SAME half, or against the half's leaf; a child off
+// every path against the same child of the OTHER half; the last position's node against the half's root.  No thread
+// reads what another writes.  No key is shifted here, so level 64 needs no care beyond tree_level_nodes_kernel's.
+// *verdict was preset to SP_PATH_TRUE on the stream: a wave that raised any bit clears the byte with one atomic on the
+// aligned word that holds it.
+__global__ void __launch_bounds__(256)
+witness_check_kernel(TreeLevels lv, const int2* __restrict__ src_all, const uint64_t* __restrict__ node,
+                     const uint64_t* __restrict__ left, const uint64_t* __restrict__ right,
+                     const uint64_t* __restrict__ hashed, const uint8_t* __restrict__ hash_status,
+                     const uint64_t* __restrict__ prev_leaves, const uint64_t* __restrict__ new_leaves,
+                     const uint64_t* __restrict__ roots, uint8_t* __restrict__ status, uint8_t* __restrict__ verdict,
+                     unsigned n_records) {
+  const unsigned u = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned st[2] = {0, 0};
+  if (u < n_records) {
+    const unsigned g = lv.cnt[0] + u;  // position in idx_all; idx_off is the running node count
+    unsigned level = 1;
+    while (level < lv.height && g >= lv.idx_off[level + 1]) ++level;
+    const int2 s2 = src_all[u];
+    const int child_base = lv.val_base[level - 1];
+    const size_t child_rec = level > 1 ? lv.idx_off[level - 1] - lv.cnt[0] : 0;  // record number of the level below's first node
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const size_t half = (size_t)h * n_records, rec = half + u;
+      const uint64_t* leaves = h ? new_leaves : prev_leaves;
+      unsigned s = hash_status[rec];
+      if (s == 0 && !felt_same(hashed + 4 * rec, node + 4 * rec)) s = SP_WITNESS_HASH_MISMATCH;
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const int at = c ? s2.y : s2.x;
+        const uint64_t* child = (c ? right : left) + 4 * rec;
+        if (at != TREE_PENDING) {
+          const size_t j = (size_t)(at - child_base);
+          const uint64_t* want = level == 1 ? leaves + 4 * j : node + 4 * (half + child_rec + j);
+          if (!felt_same(child, want)) s |= SP_WITNESS_LINK_MISMATCH;
+        } else if (h == 0 && !felt_same(child, child + 4 * (size_t)n_records)) {
+          st[1] = SP_WITNESS_SIBLING_CHANGED;  // the after record's byte starts from it
+          s |= SP_WITNESS_SIBLING_CHANGED;
+        }
+      }
+      if (u == n_records - 1 && !felt_same(node + 4 * rec, roots + 4 * h)) s |= SP_WITNESS_ROOT_MISMATCH;
+      st[h] |= s;
+      if (status) status[rec] = (uint8_t)st[h];
+    }
+  }
+  unsigned bits = st[0] | st[1];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bits |= (unsigned)__shfl_xor((int)bits, o);
+  if ((threadIdx.x & 63) == 0 && bits) {
+    const uintptr_t p = (uintptr_t)verdict;
+    atomicAnd(reinterpret_cast<unsigned*>(p & ~(uintptr_t)3), ~(0xffu << (8 * (unsigned)(p & 3))));  // SP_PATH_FALSE
   }
 }
 // ---- the leaf kernels of sp_state_batch: one thread per item, in front of the update's structure kernels ----
@@ -1184,6 +1273,194 @@ int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, ui
     std::memcpy(leaves, stage + in_bytes, n * 32);
     std::memcpy(siblings, stage + in_bytes + n * 32, pairs * 32);
   }
+  return SP_OK;
+}
+
+// ---- sp_merkle_verify_update[_dev] (include/starkperp.h): merkle_multi_update's statement (state/state.cairo:155-173)
+// checked against two witnesses, stateless.  The position structure is the update's own - tree_layout, then
+// tree_level_nodes_kernel and tree_children_kernel on the keys - one enqueue_pedersen hashes all 2 R records (both
+// halves are one contiguous array), witness_check_kernel compares. ----
+struct VerifyShape {
+  TreeLevels lv;
+  size_t total = 0, idxs = 0, records = 0;
+  unsigned top = 0;  // nodes of level `height` (1)
+};
+// The arguments both calls share; false: a bad argument, the text is in sp_last_error.  n == 0 leaves `vs` unset.
+static bool verify_update_args(unsigned height, const uint64_t* keys, size_t n, const void* prev_leaves,
+                               const void* new_leaves, const void* prev_root, const void* new_root, const void* node,
+                               const void* left, const void* right, size_t n_records, const void* verdict, VerifyShape& vs) {
+  if (height < 1 || height > 64) { set_error("height must be in 1..64"); return false; }
+  if (!prev_root || !new_root || !verdict) { set_error("sp_merkle_verify_update: null argument"); return false; }
+  if (n == 0) {
+    if (n_records != 0) { set_error("sp_merkle_verify_update: n_records is not the witness size of the keys"); return false; }
+    return true;
+  }
+  if (!keys || !prev_leaves || !new_leaves || !node || !left || !right) {
+    set_error("sp_merkle_verify_update: null argument");
+    return false;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    if (i > 0 && keys[i] <= keys[i - 1]) { set_error("keys must be strictly increasing"); return false; }
+    if (height < 64 && (keys[i] >> height) != 0) { set_error("key out of range for height"); return false; }
+  }
+  std::vector<size_t> cnt;
+  size_t felts = 0, srcs = 0;
+  if (!tree_layout(height, keys, n, cnt, vs.lv, vs.total, felts, vs.idxs, srcs) || 2 * (vs.total - n) >= 0x80000000ull) {
+    set_error("sp_merkle_verify_update: witness too large");
+    return false;
+  }
+  vs.records = vs.total - n;  // = srcs: one child list per record
+  vs.top = (unsigned)cnt[height];
+  if (n_records != vs.records) { set_error("sp_merkle_verify_update: n_records is not the witness size of the keys"); return false; }
+  return true;
+}
+static bool roots_equal(const uint64_t* a, const uint64_t* b) { return std::memcmp(a, b, 32) == 0; }
+
+// Everything on the device but keys and roots (host); enqueues on `st` and returns once both are in the stream's
+// page-locked buffer.  The caller holds the library lock (scratch map, work-buffer map, launch bookkeeping).
+static int enqueue_verify_update(const VerifyShape& vs, const uint64_t* keys, size_t n, const uint64_t* prev_leaves,
+                                 const uint64_t* new_leaves, const uint64_t* prev_root, const uint64_t* new_root,
+                                 const uint64_t* node, const uint64_t* left, const uint64_t* right, uint8_t* verdict,
+                                 uint8_t* status, hipStream_t st) {
+  const size_t R = vs.records;
+  // work buffer: roots (2 felts) | node indices, level 0 = the keys | child lists | hashes of the 2 R records | status
+  const size_t idx_off = 64, src_off = idx_off + vs.idxs * 8;
+  const size_t hash_off = (src_off + R * sizeof(int2) + 31) & ~(size_t)31, hst_off = hash_off + 2 * R * 32;
+  const size_t need = hst_off + 2 * R + 64;
+  VerifyWork& w = g_verify_work[stream_key(st)];
+  if (need > w.bytes) {
+    if (w.retired) {  // the buffer before the last one: only work older than the last growth can still read it
+      SP_HIP(hipStreamSynchronize(st));
+      (void)hipFree(w.retired);
+      w.retired = nullptr;
+    }
+    void* fresh = nullptr;
+    SP_HIP(hipMalloc(&fresh, need + need / 4));
+    w.retired = w.ptr;
+    w.ptr = fresh;
+    w.bytes = need + need / 4;
+  }
+  char* b = (char*)w.ptr;
+  uint64_t* d_roots = (uint64_t*)b;
+  uint64_t* d_idx = (uint64_t*)(b + idx_off);
+  int2* d_src = (int2*)(b + src_off);
+  uint64_t* d_hashed = (uint64_t*)(b + hash_off);
+  uint8_t* d_hst = (uint8_t*)(b + hst_off);
+  // roots and keys are adjacent on the device: one copy out of the page-locked buffer
+  if (w.pending) {
+    SP_HIP(hipEventSynchronize(w.copied));
+    w.pending = false;
+  }
+  if (w.copied == nullptr) SP_HIP(hipEventCreateWithFlags(&w.copied, hipEventDisableTiming));
+  SP_HIP(w.host.reserve(64 + n * 8));
+  std::memcpy(w.host.ptr, prev_root, 32);
+  std::memcpy((char*)w.host.ptr + 32, new_root, 32);
+  std::memcpy((char*)w.host.ptr + 64, keys, n * 8);
+  SP_HIP(hipMemcpyAsync(d_roots, w.host.ptr, 64 + n * 8, hipMemcpyHostToDevice, st));
+  SP_HIP(hipEventRecord(w.copied, st));
+  w.pending = true;
+  SP_HIP(hipMemsetAsync(verdict, SP_PATH_TRUE, 1, st));
+  hipLaunchKernelGGL(tree_level_nodes_kernel, dim3(vs.lv.height), dim3(1024), 0, st, vs.lv, d_idx, d_idx);
+  hipLaunchKernelGGL(tree_children_kernel, dim3((unsigned)((vs.total - vs.top + 255) / 256)), dim3(256), 0, st, vs.lv,
+                     d_idx, d_src, (unsigned)(vs.total - vs.top));
+  SP_HIP(hipGetLastError());
+  Scratch s;
+  int rc = get_scratch_public(2 * R, s, st);
+  if (rc != SP_OK) return rc;
+  rc = enqueue_pedersen(left, 1, right, 1, d_hashed, 1, d_hst, nullptr, 2 * R, st, s, nullptr);
+  if (rc != SP_OK) return rc;
+  hipLaunchKernelGGL(witness_check_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, vs.lv, d_src, node, left,
+                     right, d_hashed, d_hst, prev_leaves, new_leaves, d_roots, status, verdict, (unsigned)R);
+  SP_HIP(hipGetLastError());
+  return SP_OK;
+}
+
+int sp_merkle_verify_update_dev(unsigned height, const uint64_t* keys, size_t n, const uint64_t* prev_leaves,
+                                const uint64_t* new_leaves, const uint64_t* prev_root, const uint64_t* new_root,
+                                const uint64_t* node, const uint64_t* left, const uint64_t* right, size_t n_records,
+                                uint8_t* verdict, uint8_t* status, void* stream) {
+  CtxByPointer sp_ctx_sel__(verdict);  // the context of the device these pointers live on
+  SP_REQUIRE_READY();
+  VerifyShape vs;
+  if (!verify_update_args(height, keys, n, prev_leaves, new_leaves, prev_root, new_root, node, left, right, n_records,
+                          verdict, vs)) return SP_ERR_BAD_ARGUMENT;
+  if (n == 0) {
+    SP_HIP(hipMemsetAsync(verdict, roots_equal(prev_root, new_root) ? SP_PATH_TRUE : SP_PATH_FALSE, 1, (hipStream_t)stream));
+    return SP_OK;
+  }
+  ctx_lock lk(ctx().mu);
+  return enqueue_verify_update(vs, keys, n, prev_leaves, new_leaves, prev_root, new_root, node, left, right, verdict,
+                               status, (hipStream_t)stream);
+}
+
+// Host-pointer variant on a host lane: the three record arrays and the leaves up (one staged copy up to
+// PINNED_STAGE_MAX, five direct ones above it, as sp_tree_witness's results come down), one enqueue under the library
+// lock, the verdict byte - and the status bytes when asked for - down.
+int sp_merkle_verify_update(unsigned height, const uint64_t* keys, size_t n, const uint64_t* prev_leaves,
+                            const uint64_t* new_leaves, const uint64_t* prev_root, const uint64_t* new_root,
+                            const uint64_t* node, const uint64_t* left, const uint64_t* right, size_t n_records,
+                            uint8_t* verdict, uint8_t* status) {
+  LaneScope ls(0);  // the primary context, as sp_merkle_verify_paths
+  SP_REQUIRE_READY();
+  VerifyShape vs;
+  if (!verify_update_args(height, keys, n, prev_leaves, new_leaves, prev_root, new_root, node, left, right, n_records,
+                          verdict, vs)) return SP_ERR_BAD_ARGUMENT;
+  if (n == 0) {
+    *verdict = roots_equal(prev_root, new_root) ? SP_PATH_TRUE : SP_PATH_FALSE;
+    return SP_OK;
+  }
+  if (ls.open() != SP_OK) return SP_ERR_HIP;
+  HostLane& L = *ls.lane;
+  const size_t R = vs.records;
+  // device: node | left | right (2 R felts each) | previous leaves | new leaves | verdict (one word) | status bytes
+  const size_t rec_bytes = 2 * R * 32, leaf_bytes = n * 32, in_bytes = 3 * rec_bytes + 2 * leaf_bytes;
+  const size_t out_bytes = 4 + (status ? 2 * R : 0);
+  SP_HIP(L.io.reserve(in_bytes + 4 + 2 * R + 64));
+  char* b = (char*)L.io.ptr;
+  uint64_t* d_node = (uint64_t*)b;
+  uint64_t* d_left = d_node + 8 * R;
+  uint64_t* d_right = d_left + 8 * R;
+  uint64_t* d_prev = d_right + 8 * R;
+  uint64_t* d_new = d_prev + 4 * n;
+  uint8_t* d_verdict = (uint8_t*)(b + in_bytes);
+  uint8_t* d_status = d_verdict + 4;
+  char* stage = nullptr;
+  if (in_bytes + out_bytes <= PINNED_STAGE_MAX && L.hio.reserve(in_bytes + out_bytes) == hipSuccess) stage = (char*)L.hio.ptr;
+  else (void)hipGetLastError();
+  if (stage) {
+    std::memcpy(stage, node, rec_bytes);
+    std::memcpy(stage + rec_bytes, left, rec_bytes);
+    std::memcpy(stage + 2 * rec_bytes, right, rec_bytes);
+    std::memcpy(stage + 3 * rec_bytes, prev_leaves, leaf_bytes);
+    std::memcpy(stage + 3 * rec_bytes + leaf_bytes, new_leaves, leaf_bytes);
+    SP_HIP(hipMemcpyAsync(d_node, stage, in_bytes, hipMemcpyHostToDevice, L.stream));
+  } else {
+    SP_HIP(hipMemcpyAsync(d_node, node, rec_bytes, hipMemcpyHostToDevice, L.stream));
+    SP_HIP(hipMemcpyAsync(d_left, left, rec_bytes, hipMemcpyHostToDevice, L.stream));
+    SP_HIP(hipMemcpyAsync(d_right, right, rec_bytes, hipMemcpyHostToDevice, L.stream));
+    SP_HIP(hipMemcpyAsync(d_prev, prev_leaves, leaf_bytes, hipMemcpyHostToDevice, L.stream));
+    SP_HIP(hipMemcpyAsync(d_new, new_leaves, leaf_bytes, hipMemcpyHostToDevice, L.stream));
+  }
+  int rc;
+  {
+    ctx_lock lk(ctx().mu);
+    rc = enqueue_verify_update(vs, keys, n, d_prev, d_new, prev_root, new_root, d_node, d_left, d_right, d_verdict,
+                               d_status, L.stream);
+  }
+  if (rc != SP_OK) return rc;
+  uint8_t v = SP_PATH_FALSE;  // written by the stream, read after the synchronisation below
+  if (stage) {
+    SP_HIP(hipMemcpyAsync(stage + in_bytes, d_verdict, out_bytes, hipMemcpyDeviceToHost, L.stream));
+  } else {
+    SP_HIP(hipMemcpyAsync(&v, d_verdict, 1, hipMemcpyDeviceToHost, L.stream));
+    if (status) SP_HIP(hipMemcpyAsync(status, d_status, 2 * R, hipMemcpyDeviceToHost, L.stream));
+  }
+  SP_HIP(hipStreamSynchronize(L.stream));
+  if (stage) {
+    v = (uint8_t)stage[in_bytes];
+    if (status) std::memcpy(status, stage + in_bytes + 4, 2 * R);
+  }
+  *verdict = v;
   return SP_OK;
 }
 

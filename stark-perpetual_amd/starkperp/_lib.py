@@ -52,6 +52,10 @@ _SIGNATURES = {
     "sp_merkle_verify_paths": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint,
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                               ctypes.c_void_p, ctypes.c_void_p]),
+    "sp_merkle_verify_update": (ctypes.c_int, [ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 7
+                                + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "sp_merkle_verify_update_dev": (ctypes.c_int, [ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 7
+                                    + [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sp_merkle_root": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p]),
     "sp_merkle_build_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),

@@ -10,6 +10,8 @@ FIELD_PRIME = 2**251 + 17 * 2**192 + 1
 EC_ORDER = 0x800000000000010FFFFFFFFFFFFFFFFB781126DCAE7B2321E66A241ADC64D2F
 
 HASH_OK, HASH_OUT_OF_RANGE, HASH_UNHASHABLE = 0, 1, 2
+# include/starkperp.h SP_WITNESS_*: per-record status bits of sp_merkle_verify_update, beside the two HASH_* bits
+WITNESS_HASH_MISMATCH, WITNESS_LINK_MISMATCH, WITNESS_SIBLING_CHANGED, WITNESS_ROOT_MISMATCH = 0x04, 0x08, 0x20, 0x40
 
 
 def _raise_hash_status(code):

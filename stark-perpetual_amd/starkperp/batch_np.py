@@ -9,7 +9,8 @@ import numpy as np
 
 from . import _lib
 from .batch import (EC_ORDER, FIELD_PRIME, HASH_OUT_OF_RANGE, HASH_UNHASHABLE, SIGN_BAD_INPUT, SIGN_OK, SIGN_RETRY,
-                    VERIFY_TRUE, _raise_hash_status, raise_for_verify_code)
+                    VERIFY_TRUE, WITNESS_HASH_MISMATCH, WITNESS_LINK_MISMATCH, WITNESS_ROOT_MISMATCH,
+                    WITNESS_SIBLING_CHANGED, _raise_hash_status, raise_for_verify_code)
 
 _P_LIMBS = np.array([(FIELD_PRIME >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
 
@@ -364,3 +365,32 @@ def tree_prove(tree, keys):
     _lib.check(_lib.ensure_init().sp_tree_prove(tree._handle, _ptr(keys), n, _ptr(leaves), _ptr(siblings)),
                "sp_tree_prove")
     return leaves, siblings
+
+
+def merkle_verify_update(height, keys, prev_leaves, new_leaves, prev_root, new_root, before, after):
+    """The statement of merkle_multi_update(prev_leaves, new_leaves, height, prev_root, new_root)
+    (state/state.cairo:155-173) checked against two witnesses in ONE library call (sp_merkle_verify_update): every
+    record hashed once in a bulk launch, the links between the records, the leaves, the roots and the untouched siblings
+    compared on the device.
+      keys uint64[n] strictly increasing; prev_leaves, new_leaves uint64[n, 4]; prev_root, new_root ints or uint64[4]
+      before, after   the tuples tree_witness returned for `keys` before and after the update (level and index are
+                      not read: the library derives every position from the keys)
+    Returns (verdict bool, status uint8[2, R]): status[0] for the before records, status[1] for the after records, a
+    byte being the OR of HASH_OUT_OF_RANGE, HASH_UNHASHABLE and the WITNESS_* bits of starkperp.batch; the verdict is
+    True iff every byte is 0.  Nothing is raised for a data-dependent outcome."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    assert keys.ndim == 1
+    n = keys.shape[0]
+    prev_leaves, new_leaves = _felts(prev_leaves, n), _felts(new_leaves, n)
+    roots = [felts_from_ints([r]) if isinstance(r, int) else _felts(np.reshape(r, (1, 4)), 1) for r in (prev_root, new_root)]
+    node, left, right = (np.ascontiguousarray(np.concatenate([_felts(before[i]), _felts(after[i])]))
+                         for i in (2, 3, 4))
+    records = _felts(before[2]).shape[0]
+    assert _felts(after[2]).shape[0] == records and left.shape[0] == 2 * records and right.shape[0] == 2 * records, \
+        "before and after hold the same number of records"
+    verdict = np.zeros(1, dtype=np.uint8)
+    status = np.zeros((2, records), dtype=np.uint8)
+    _lib.check(_lib.ensure_init().sp_merkle_verify_update(
+        height, _ptr(keys), n, _ptr(prev_leaves), _ptr(new_leaves), _ptr(roots[0]), _ptr(roots[1]), _ptr(node),
+        _ptr(left), _ptr(right), records, _ptr(verdict), _ptr(status)), "sp_merkle_verify_update")
+    return bool(verdict[0] == 1), status

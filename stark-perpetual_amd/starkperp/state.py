@@ -193,6 +193,133 @@ def facts_of(witness) -> Dict[int, Tuple[int, int]]:
     return {node: (left, right) for _, _, node, left, right in witness}
 
 
+def records_from_facts(facts, root: int, height: int, keys: Iterable[int]) -> List[Tuple[int, int, int, int, int]]:
+    """The reference's dictionary {node: (left, right)} -> witness records of `keys` under `root`, in witness order
+    (level 1 .. height, ascending index inside a level): the walk down from the root along the subtree induced by the
+    keys (merkle_tree.py:4-26), nothing hashed.  KeyError: a preimage is missing."""
+    keys = sorted(set(keys))
+    for k in keys:
+        assert 0 <= k < (1 << height), "key out of range for height"
+    if not keys:
+        return []
+    levels: List[List[Tuple[int, int, int, int, int]]] = [[] for _ in range(height + 1)]
+    values = {0: root}
+    for level in range(height, 0, -1):
+        below = {}
+        for idx in sorted(set(k >> level for k in keys)):
+            left, right = facts[values[idx]]
+            levels[level].append((level, idx, values[idx], left, right))
+            below[2 * idx], below[2 * idx + 1] = left, right
+        values = below
+    return [rec for level in levels for rec in level]
+
+
+def _hash_records(records, hash_many):
+    """(hashes, status) of H(left, right) per record, the status as the library reports it: HASH_OUT_OF_RANGE for a
+    child outside [0, p) (nothing is hashed then), HASH_UNHASHABLE where the hash itself raises."""
+    status = [batch.HASH_OK if 0 <= rec[3] < batch.FIELD_PRIME and 0 <= rec[4] < batch.FIELD_PRIME
+              else batch.HASH_OUT_OF_RANGE for rec in records]
+    todo = [u for u, st in enumerate(status) if st == batch.HASH_OK]
+    hashes = [None] * len(records)
+    try:
+        done = hash_many([records[u][3] for u in todo], [records[u][4] for u in todo]) if todo else []
+        for u, hv in zip(todo, done):
+            hashes[u] = hv
+    except AssertionError:  # "Unhashable input." somewhere in the batch: one by one, to know where
+        for u in todo:
+            try:
+                hashes[u] = hash_many([records[u][3]], [records[u][4]])[0]
+            except AssertionError:
+                status[u] = batch.HASH_UNHASHABLE
+    return hashes, status
+
+
+def verify_update_records(height: int, keys: Sequence[int], prev_leaves: Sequence[int], new_leaves: Sequence[int],
+                          prev_root: int, new_root: int, before, after, hash_many):
+    """Host twin of sp_merkle_verify_update (include/starkperp.h), the same status bits computed in plain Python with
+    every hash through `hash_many`: the statement of merkle_multi_update(prev_leaves, new_leaves, height, prev_root,
+    new_root) (state/state.cairo:155-173) against the witness records `before` and `after` ((level, index, node, left,
+    right) in witness order; level and index are NOT read - the positions follow from the strictly increasing `keys`
+    alone, as in the library).  Returns (verdict, [status of the before records, status of the after records]): per
+    record the OR of HASH_OUT_OF_RANGE / HASH_UNHASHABLE (from hashing left, right), WITNESS_HASH_MISMATCH (the hash has
+    status 0 and is not the node), WITNESS_LINK_MISMATCH (a child on a key's path is not the node of the record below
+    it in the same half - at level 1 not that key's leaf), WITNESS_SIBLING_CHANGED (a child on no key's path differs
+    between the two records of the position; on both) and WITNESS_ROOT_MISMATCH (last record: the node is not the
+    half's root).  The verdict is True iff every status is 0; without keys it is prev_root == new_root."""
+    keys = list(keys)
+    assert 1 <= height <= 64, "height must be in 1..64"
+    assert all(0 <= k < (1 << height) for k in keys), "key out of range for height"
+    assert all(a < b for a, b in zip(keys, keys[1:])), "keys must be strictly increasing"
+    assert len(prev_leaves) == len(keys) and len(new_leaves) == len(keys)
+    layout = [(level, idx) for level in range(1, height + 1) for idx in sorted({k >> level for k in keys})]
+    records = len(layout)
+    assert len(before) == records and len(after) == records, "n_records is not the witness size of the keys"
+    if not keys:
+        return prev_root == new_root, [[], []]
+    place = {pos: u for u, pos in enumerate(layout)}
+    leaf_at = {k: j for j, k in enumerate(keys)}
+    halves, leaves, roots = (before, after), (prev_leaves, new_leaves), (prev_root, new_root)
+    status = []
+    for h in (0, 1):
+        hashes, st = _hash_records(halves[h], hash_many)
+        for u, (level, idx) in enumerate(layout):
+            _, _, node, left, right = halves[h][u]
+            if st[u] == batch.HASH_OK and hashes[u] != node:
+                st[u] |= batch.WITNESS_HASH_MISMATCH
+            for c, child in enumerate((left, right)):
+                pos = (level - 1, 2 * idx + c)
+                if level == 1 and pos[1] in leaf_at:
+                    linked = child == leaves[h][leaf_at[pos[1]]]
+                elif level > 1 and pos in place:
+                    linked = child == halves[h][place[pos]][2]
+                else:  # on no key's path: the same value before and after
+                    linked = True
+                    if before[u][3 + c] != after[u][3 + c]:
+                        st[u] |= batch.WITNESS_SIBLING_CHANGED
+                if not linked:
+                    st[u] |= batch.WITNESS_LINK_MISMATCH
+        if halves[h][-1][2] != roots[h]:
+            st[-1] |= batch.WITNESS_ROOT_MISMATCH
+        status.append(st)
+    return not any(status[0]) and not any(status[1]), status
+
+
+def _record_arrays(records):
+    """Witness records (tuples of ints) -> the arrays batch_np.tree_witness returns."""
+    import numpy as np
+    from .batch_np import felts_from_ints
+    felts = lambda i: felts_from_ints([rec[i] for rec in records]) if records else np.zeros((0, 4), dtype=np.uint64)
+    return (np.array([rec[0] for rec in records], dtype=np.uint8), np.array([rec[1] for rec in records], dtype=np.uint64),
+            felts(2), felts(3), felts(4))
+
+
+def _verify_records(height, keys, prev_leaves, new_leaves, prev_root, new_root, before, after, hash_many) -> bool:
+    """One verdict for records given as tuples: the host twin with an injected hash, else ONE library call."""
+    if hash_many is not None:
+        return verify_update_records(height, keys, prev_leaves, new_leaves, prev_root, new_root, before, after,
+                                     hash_many)[0]
+    import numpy as np
+    from . import batch_np
+    felts = lambda values: batch_np.felts_from_ints(values) if values else np.zeros((0, 4), dtype=np.uint64)
+    return batch_np.merkle_verify_update(height, np.array(keys, dtype=np.uint64), felts(list(prev_leaves)),
+                                         felts(list(new_leaves)), prev_root, new_root, _record_arrays(before),
+                                         _record_arrays(after))[0]
+
+
+def verify_multi_update(facts, height: int, prev_root: int, new_root: int, modifications, hash_many=None) -> bool:
+    """The statement of merkle_multi_update (state/state.cairo:155-173) for modifications = {key: (prev_leaf,
+    new_leaf)}: whether `facts` ({node: (left, right)}, program_input['merkle_facts']) carries a tree of root
+    prev_root holding the previous leaves, a tree of root new_root holding the new ones, and nothing else differs
+    between the two.  The records are read out of `facts` from both roots (records_from_facts: KeyError for a missing
+    preimage) and checked in ONE library call (sp_merkle_verify_update: every record hashed once, no dependent chain);
+    with an injected `hash_many` the host twin verify_update_records does the same."""
+    keys = sorted(modifications)
+    before = records_from_facts(facts, prev_root, height, keys)
+    after = records_from_facts(facts, new_root, height, keys)
+    return _verify_records(height, keys, [modifications[k][0] for k in keys], [modifications[k][1] for k in keys],
+                           prev_root, new_root, before, after, hash_many)
+
+
 def proof_root(key: int, leaf: int, siblings: Sequence[int], hash_many) -> int:
     """Folds an inclusion proof (SparseMerkleTree.prove / LibrarySparseTree.prove) to the root it commits to."""
     node = leaf
@@ -285,6 +412,26 @@ class LibrarySparseTree:
         if st[0]:
             raise AssertionError("Unhashable input." if st[0] & 2 else "leaf out of range")
         return self._lib.unpack_felts(old, 1)[0], self._lib.unpack_felts(new, 1)[0]
+
+    def update_checked(self, modifications: Dict[int, int]) -> Tuple[int, int]:
+        """`update` with its own audit: the witness of the keys before, the update, the witness after, and ONE
+        sp_merkle_verify_update call on the two (previous leaves from sp_tree_get) - the statement of
+        merkle_multi_update for exactly this batch.  Returns (old_root, new_root); AssertionError when the verdict is
+        false (the update has been written by then)."""
+        import numpy as np
+        from . import batch_np
+        items = sorted(dict(modifications).items())
+        if not items:
+            return self.update({})
+        keys = np.array([k for k, _ in items], dtype=np.uint64)
+        prev = batch_np.felts_from_ints(self.get_many([k for k, _ in items]))
+        before = batch_np.tree_witness(self, keys)
+        old_root, new_root = self.update(dict(items))
+        after = batch_np.tree_witness(self, keys)
+        ok, status = batch_np.merkle_verify_update(self.height, keys, prev, batch_np.felts_from_ints([v for _, v in items]),
+                                                   old_root, new_root, before, after)
+        assert ok, "the witnesses do not verify the update (status bits 0x%02x)" % int(np.bitwise_or.reduce(status, axis=None))
+        return old_root, new_root
 
     def witness(self, keys: Iterable[int]) -> List[Tuple[int, int, int, int, int]]:
         """As SparseMerkleTree.witness, read from the library's node table in one call (sp_tree_witness)."""
@@ -407,6 +554,7 @@ class SharedState:
     def __init__(self, positions_tree_height: int = 64, orders_tree_height: int = 64, hash_many=None,
                  position_hashes=None):
         self._position_hashes = position_hashes or position_hashes_many
+        self._hash_many = hash_many  # None: the library checks collected facts (check_facts), else the host twin does
         empty_leaf = self._position_hashes([self.EMPTY_POSITION])[0]
         if hash_many is None:  # the library keeps the trees: one call per update
             self.positions = LibrarySparseTree(positions_tree_height, empty_leaf)
@@ -423,7 +571,7 @@ class SharedState:
     def orders_root(self) -> int:
         return self.orders.root
 
-    def apply_state_updates(self, position_accesses, order_accesses, facts=None):
+    def apply_state_updates(self, position_accesses, order_accesses, facts=None, check_facts=False):
         """shared_state_apply_state_updates (state/state.cairo:135-186): squash, hash the previous
         and new positions (hash_position_updates), check the previous leaves against the tree,
         merkle-multi-update both trees.  Returns ((old_pos_root, new_pos_root), (old_ord, new_ord)).
@@ -431,22 +579,32 @@ class SharedState:
         _apply_in_one_call); with an injected hash the steps are separate calls (_apply_in_separate_calls).
         facts: a dict that receives the batch's merkle_facts (main.cairo:39-40, 61-64) for both trees - the witness
         of the squashed keys before the update and again after it, {node: (left, right)} - merged in only when the
-        batch commits: a batch that raises leaves the dict as it was.  None: nothing is read back."""
+        batch commits: a batch that raises leaves the dict as it was.  None: nothing is read back.
+        check_facts (with facts): both trees' collected witnesses are verified against the batch's roots and the trees'
+        leaves at the squashed keys before and after (the statement of merkle_multi_update, one
+        sp_merkle_verify_update call per tree, or verify_update_records with an injected hash) BEFORE they are merged
+        into the dict; AssertionError, with the dict as it was, when one does not verify."""
         if (isinstance(self.positions, LibrarySparseTree) and isinstance(self.orders, LibrarySparseTree)
                 and self._position_hashes is position_hashes_many):
             apply = self._apply_in_one_call
         else:
             apply = self._apply_in_separate_calls
         if facts is None:
+            assert not check_facts, "check_facts needs a facts dict"
             return apply(position_accesses, order_accesses)
         touched = [(self.positions, [key for key, _, _ in squash_updates(position_accesses)]),
                    (self.orders, [key for key, _, _ in squash_updates(order_accesses)])]
         collected: Dict[int, Tuple[int, int]] = {}
-        for tree, keys in touched:
-            collected.update(facts_of(tree.witness(keys)))
+        prev_leaves = [tree.get_many(keys) if check_facts else None for tree, keys in touched]
+        before = [tree.witness(keys) for tree, keys in touched]
         roots = apply(position_accesses, order_accesses)
-        for tree, keys in touched:
-            collected.update(facts_of(tree.witness(keys)))
+        after = [tree.witness(keys) for tree, keys in touched]
+        for (tree, keys), prev, wit_b, wit_a, (old_root, new_root) in zip(touched, prev_leaves, before, after, roots):
+            if check_facts:
+                assert _verify_records(tree.height, keys, prev, tree.get_many(keys), old_root, new_root, wit_b, wit_a,
+                                       self._hash_many), "the collected merkle_facts do not verify the batch"
+            collected.update(facts_of(wit_b))
+            collected.update(facts_of(wit_a))
         facts.update(collected)
         return roots
 
