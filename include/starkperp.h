@@ -226,6 +226,35 @@ int sp_tree_witness(int tree, const uint64_t* keys, size_t n, size_t capacity, u
  * sp_tree_root.  A key out of range or an unknown handle: SP_ERR_BAD_ARGUMENT, nothing written.  Same locking and
  * copy-back as sp_tree_witness; n x height (key, level) pairs must stay below 2^31. */
 int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, uint64_t* siblings);
+/* Ordered range scan: WHICH keys the tree holds.  Writes the first min(capacity, SP_TREE_SCAN_MAX, count) keys k with
+ * lo <= k <= hi (both bounds inclusive, so 2^64 - 1 is reachable), ascending, whose leaf differs from the tree's empty
+ * leaf; leaves receives the matching leaves (*n felts), *n the number written.  *more = 1 if and only if at least one
+ * further such key exists in the range: resume with lo = keys[*n - 1] + 1.  A leaf that was written with the empty
+ * leaf's value - never written, or set back - is not reported.  Host pointers, synchronous; locking and device
+ * selection as sp_tree_get, so a page always describes a batch boundary.
+ * The device walks down from the root, one step per level: the frontier of level l is the ascending list of nodes
+ * whose key interval meets [lo, hi] and whose value differs from the empty-subtree root of level l; the frontier of
+ * level 0 is the answer.  (1) Pruning compares VALUES, not presence: a leaf set back to the empty leaf leaves its path
+ * in the table with empty-root values, and only a node that differs from its level's empty root has a live leaf below
+ * it.  (2) Hence a frontier may be cut at any level - above level 0 to its first capacity + 2 nodes, since only the
+ * first and the last node of a frontier can stick out of [lo, hi] and hold no leaf IN RANGE, so the first `capacity`
+ * leaves lie below what is kept - and a cut at any level means `more`.  (3) No node interval is computed with a shift by
+ * 64: the root's interval is "everything" and is never tested.
+ * SP_ERR_BAD_ARGUMENT, with nothing written: lo > hi, hi >= 2^height when height < 64, capacity == 0, a null pointer,
+ * an unknown or destroyed handle.  A tree that has never been updated, or whose root is the empty root, answers
+ * *n = 0, *more = 0 without a launch.
+ * Cost: proportional to height x *n table probes (one launch per level once the frontier is wider than one
+ * workgroup, one launch for the narrow top; a page of up to 1022 keys is one launch), never to the size of the table;
+ * one copy back (count, more, keys, leaves) through the tree's page-locked buffer for a page up to 4 MiB, above that
+ * the count first and then exactly *n keys and leaves.  Measured numbers: DESIGN.md 4.8, tools/quick_tree_scan.py,
+ * profiles/tree_scan.txt. */
+/* capacity above SP_TREE_SCAN_MAX is treated as SP_TREE_SCAN_MAX: page with `more` */
+#define SP_TREE_SCAN_MAX ((size_t)1 << 22)
+int sp_tree_scan(int tree, uint64_t lo, uint64_t hi, size_t capacity,
+                 uint64_t* keys, uint64_t* leaves, size_t* n, int* more);
+/* The tree's node table as it stands: *entries = slots in use (nodes ever written, at any level: it never shrinks, a
+ * leaf set back to the empty leaf keeps its path), *slots = the table's slot count (48 bytes each).  Read-only. */
+int sp_tree_table_size(int tree, uint64_t* entries, uint64_t* slots);
 /* Verifying inclusion proofs: Merkle paths folded on the device, all of a call in ONE launch (ped_fold_ragged_kernel)
  * that lasts as long as its longest path.  node = pedersen_hash(left, right) (signature.py:296-318); bit l of keys[i]
  * says whether the running node is the RIGHT child at level l (starkware/python/merkle_tree.py:4-26,
@@ -301,7 +330,8 @@ int sp_merkle_verify_update(unsigned height, const uint64_t* keys, size_t n, con
                             const uint64_t* new_leaves, const uint64_t* prev_root, const uint64_t* new_root,
                             const uint64_t* node, const uint64_t* left, const uint64_t* right, size_t n_records,
                             uint8_t* verdict, uint8_t* status);
-/* Threading of the sp_tree_* calls: a tree has its own HIP stream, work buffer and mutex.  An operation holds
+/* Threading of the sp_tree_* calls (sp_tree_update, sp_tree_get, sp_tree_root, sp_tree_witness, sp_tree_prove,
+ * sp_tree_scan, sp_tree_table_size, sp_tree_destroy): a tree has its own HIP stream, work buffer and mutex.  An operation holds
  * the tree's mutex from start to end and the library lock only while it enqueues; the device work of an update
  * (the level launches) runs without the library lock, so other trees and the stateless batches go on meanwhile. */
 /* BASELINE.json configs[2] in one call (services/perpetual/cairo/order/limit_order.cairo:24-52, order.cairo:23-31,

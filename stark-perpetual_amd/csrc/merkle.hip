@@ -569,6 +569,269 @@ tree_rehash_kernel(const TreeSlot* __restrict__ old, uint64_t old_slots, TreeSlo
   if (sl.state == 2) (void)tree_put(tab, mask, sl.level1 - 1, sl.index, sl.value);
 }
 
+// ---- ordered range scan of the non-empty leaves (sp_tree_scan): a descent from the root, no sweep of the table ----
+// The frontier of level l is the ascending list of node indices at level l whose key interval meets [lo, hi] and
+// whose value differs from the level's empty-subtree root; one step takes it to level l - 1, the frontier of level 0
+// is the answer.  What carries the correctness:
+//   1. PRUNING COMPARES VALUES (scan_keeps): a leaf that was written and later set back to the empty leaf leaves its
+//      whole path in the table, holding empty-subtree roots.  A node that merely exists may have no live leaf below
+//      it; a node whose value differs from its level's empty root has at least one.
+//   2. so the CUT IS SAFE, with a margin of two: a kept node has a live leaf below it, and that leaf is in range
+//      unless the node's interval sticks out of [lo, hi] - which only the node that holds lo (the first of its
+//      frontier) and the node that holds hi (the last) can do.  A frontier above level 0 is therefore cut to its
+//      first cap + 2 nodes (scan_limit): a frontier that was cut has lost its last node, so at most one node kept
+//      is dead, at least cap + 1 have a leaf in range - the first `cap` leaves lie below them, and a cut at ANY level
+//      means `more`.  Level 0 holds keys in range only and is cut to cap.  (A cut to cap alone returns an empty page
+//      with `more` set for lo = previous key + 1, cap = 1: the node that holds the previous key takes the place.)
+//   3. SHIFTS: only children are probed, so a level that is shifted by is at most 63; scan_meets still guards
+//      level < 64 the way tree_level_nodes_kernel does, and the root (level 64: "everything") is never tested.
+// Work buffer (sp_tree_scan lays it out): header | frontier 0 = the keys | leaves | frontier 1 | mark bytes 0 / 1 |
+// cnt[65] | tot[height + 1][blocks]; frontiers and marks have cap + 2 places.  Level l uses frontier, marks of parity l & 1.  A node's MARK byte says which of
+// its two children are kept (bit 0 left, bit 1 right): it is written by the thread that emits the node, which probes
+// the node's children then and there - every node is probed once, by the launch that places it - and adds their number
+// to tot[l][position >> 8] (integer atomics: the sum does not depend on the order).  cnt and tot are cleared once per
+// call.  Launches: tree_scan_top_kernel walks the narrow top in ONE workgroup while the frontier fits its 1024
+// threads; below that one tree_scan_step_kernel launch per level, grids sized from cap + 2 (which bounds every
+// frontier): a block reads the live length on the device and leaves when it has no node.  No level comes back to the
+// host.
+struct ScanHeader {          // 16 bytes, copied back in front of the keys
+  unsigned long long n;      // keys found, at most cap
+  unsigned more;             // a frontier was cut: further keys exist in the range
+  unsigned start;            // the level at which the top kernel handed over (0: it finished the descent)
+};
+constexpr unsigned SCAN_TOP = 1024;   // threads of the top kernel = the widest frontier it steps from
+constexpr unsigned SCAN_BLOCK = 256;  // threads of a step block = frontier nodes per tot[] entry
+struct ScanWork {
+  const TreeSlot* tab;
+  uint64_t mask;
+  const uint64_t* emp;       // empty-subtree roots of levels 0 .. height
+  uint64_t lo, hi;
+  unsigned cap, blocks;      // blocks = ceil((cap + 2) / SCAN_BLOCK): entries of tot per level
+  ScanHeader* hdr;
+  uint64_t* frontier[2];
+  uint8_t* marks[2];
+  unsigned* cnt;             // live frontier length per level (below the hand-over)
+  unsigned* tot;             // kept children per SCAN_BLOCK nodes of a level's frontier
+  uint64_t* leaves;
+};
+// property 2: how many nodes the frontier of `level` keeps
+__device__ __forceinline__ unsigned scan_limit(const ScanWork& w, unsigned level) { return level ? w.cap + 2 : w.cap; }
+__device__ __forceinline__ bool scan_meets(uint64_t index, unsigned level, uint64_t lo, uint64_t hi) {
+  const uint64_t first = level < 64 ? index << level : 0;
+  const uint64_t last = level < 64 ? first | ((1ull << level) - 1ull) : ~0ull;
+  return first <= hi && last >= lo;
+}
+// A whole slot in three 16-byte loads whose addresses are known before any of them returns: a probe costs ONE trip to
+// memory, and the two children of a node are probed side by side.  (tree_find reads state, then level and index, then
+// the value, each behind a branch on the one before.  Measured gain over two tree_find calls: 2.29 -> 2.21 ms per
+// 4096-key page while the atomics still dominated, 0.43 -> 0.36 ms per 256-key page)
+struct ScanSlot {
+  uint4 head;  // x, y: index; z: level + 1; w: state
+  uint4 v[2];
+};
+__device__ __forceinline__ ScanSlot scan_load(const TreeSlot* tab, uint64_t i) {
+  const uint4* p = reinterpret_cast<const uint4*>(tab + i);  // 48-byte slots of a 256-byte aligned table
+  ScanSlot s;
+  s.head = p[0];
+  s.v[0] = p[1];
+  s.v[1] = p[2];
+  return s;
+}
+// property 1: present AND different from the level's empty root (e0, e1); `s` is the slot at the key's home `i`.
+// Lookups never run beside insertions (different launches of one stream), so a slot is empty or ready.
+// (Loading runs of four consecutive slots per probe was measured and dropped: DESIGN.md 11.)
+__device__ __forceinline__ bool scan_keeps(const ScanWork& w, unsigned level, uint64_t index, uint64_t i, ScanSlot s,
+                                           uint4 e0, uint4 e1) {
+  for (;;) {
+    if (s.head.w == 0) return false;
+    if (s.head.w == 2 && s.head.z == level + 1 && s.head.x == (uint32_t)index && s.head.y == (uint32_t)(index >> 32)) {
+      const uint32_t d = (s.v[0].x ^ e0.x) | (s.v[0].y ^ e0.y) | (s.v[0].z ^ e0.z) | (s.v[0].w ^ e0.w) |
+                         (s.v[1].x ^ e1.x) | (s.v[1].y ^ e1.y) | (s.v[1].z ^ e1.z) | (s.v[1].w ^ e1.w);
+      return d != 0;
+    }
+    i = (i + 1) & w.mask;
+    s = scan_load(w.tab, i);
+  }
+}
+// which children of node (level, index), level >= 1, are kept: both home slots and the empty root are loaded at once
+__device__ __forceinline__ unsigned scan_mark(const ScanWork& w, unsigned level, uint64_t index) {
+  const unsigned below = level - 1;
+  const uint64_t il = tree_mix(2 * index, below) & w.mask, ir = tree_mix(2 * index + 1, below) & w.mask;
+  const ScanSlot sl = scan_load(w.tab, il), sr = scan_load(w.tab, ir);
+  const uint4* e = reinterpret_cast<const uint4*>(w.emp + 4 * below);
+  const uint4 e0 = e[0], e1 = e[1];
+  unsigned mark = 0;
+  if (scan_meets(2 * index, below, w.lo, w.hi) && scan_keeps(w, below, 2 * index, il, sl, e0, e1)) mark |= 1u;
+  if (scan_meets(2 * index + 1, below, w.lo, w.hi) && scan_keeps(w, below, 2 * index + 1, ir, sr, e0, e1)) mark |= 2u;
+  return mark;
+}
+// key and leaf of position p of the answer (a kept node of level 0 is in the table)
+__device__ __forceinline__ void scan_leaf(const ScanWork& w, uint64_t key, unsigned p) {
+  uint64_t i = tree_mix(key, 0) & w.mask;
+  ScanSlot s = scan_load(w.tab, i);
+  while (s.head.w != 0 &&
+         !(s.head.w == 2 && s.head.z == 1 && s.head.x == (uint32_t)key && s.head.y == (uint32_t)(key >> 32))) {
+    i = (i + 1) & w.mask;
+    s = scan_load(w.tab, i);
+  }
+  uint64_t* out = w.leaves + 4 * (size_t)p;  // 8-byte aligned only: cap + 2 keys lie in front
+  if (s.head.w != 0) {
+    out[0] = s.v[0].x | (uint64_t)s.v[0].y << 32;
+    out[1] = s.v[0].z | (uint64_t)s.v[0].w << 32;
+    out[2] = s.v[1].x | (uint64_t)s.v[1].y << 32;
+    out[3] = s.v[1].z | (uint64_t)s.v[1].w << 32;
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) out[q] = w.emp[q];
+  }
+}
+__device__ __forceinline__ unsigned scan_wave_sum(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o);
+  return v;
+}
+__global__ void __launch_bounds__(SCAN_TOP)
+tree_scan_top_kernel(ScanWork w, unsigned height) {
+  __shared__ unsigned wave_tot[SCAN_TOP / 64];
+  // the frontiers of the top live in LDS (2 x 16 KiB), not in the work buffer: no trip to L2 between two levels
+  // (measured: 2 % of a 256-key page)
+  __shared__ uint64_t fr[2][2 * SCAN_TOP];
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned level = height, cnt = 1, more = 0;
+  if (threadIdx.x == 0) fr[height & 1][0] = 0;  // the root; the host has compared it with the empty root
+  __syncthreads();
+  while (level > 0 && cnt <= SCAN_TOP) {
+    const uint64_t* cur = fr[level & 1];
+    uint64_t* next = fr[(level - 1) & 1];  // total <= 2 cnt <= 2 SCAN_TOP places are written
+    const bool live = threadIdx.x < cnt;
+    const uint64_t me = live ? cur[threadIdx.x] : 0;
+    const unsigned mark = live ? scan_mark(w, level, me) : 0;
+    const unsigned long long bl = __ballot(mark & 1), br = __ballot(mark & 2);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned before = __popcll(bl & below) + __popcll(br & below);
+    if (lane == 0) wave_tot[wave] = __popcll(bl) + __popcll(br);
+    __syncthreads();
+    unsigned p = before, total = 0;
+    for (unsigned v = 0; v < SCAN_TOP / 64; ++v) {
+      if (v < wave) p += wave_tot[v];
+      total += wave_tot[v];
+    }
+    const unsigned limit = scan_limit(w, level - 1);
+    if ((mark & 1) && p < limit) next[p] = 2 * me;
+    p += mark & 1;
+    if ((mark & 2) && p < limit) next[p] = 2 * me + 1;
+    if (total > limit) more = 1;  // property 2: a cut at any level
+    cnt = total < limit ? total : limit;
+    --level;
+    __syncthreads();  // next[] is read by other threads, wave_tot is written again
+    if (cnt == 0) level = 0;  // nothing in range: the answer is empty
+  }
+  if (level == 0) {  // cnt <= min(cap, 2 SCAN_TOP) keys in frontier 0: their leaves
+    for (unsigned i = threadIdx.x; i < cnt; i += SCAN_TOP) {
+      const uint64_t key = fr[0][i];
+      w.frontier[0][i] = key;
+      scan_leaf(w, key, i);
+    }
+  } else {           // hand over at `level`: marks and totals of its frontier, as a step launch would have left them
+    const uint64_t* cur = fr[level & 1];
+    for (unsigned base = 0; base < cnt; base += SCAN_TOP) {
+      const unsigned i = base + threadIdx.x;  // the 64 nodes of a wave lie in one SCAN_BLOCK: one atomic per wave
+      const unsigned mark = i < cnt ? scan_mark(w, level, cur[i]) : 0;
+      if (i < cnt) {
+        w.frontier[level & 1][i] = cur[i];
+        w.marks[level & 1][i] = (uint8_t)mark;
+      }
+      const unsigned kept = scan_wave_sum((unsigned)__popc(mark));
+      if (lane == 0 && kept) atomicAdd(&w.tot[(size_t)level * w.blocks + i / SCAN_BLOCK], kept);
+    }
+  }
+  if (threadIdx.x == 0) {
+    w.hdr->n = level == 0 ? cnt : 0;
+    w.hdr->more = more;
+    w.hdr->start = level;
+    if (level) w.cnt[level] = cnt;
+  }
+}
+// One step, level -> level - 1, one thread per frontier node.  A block sums the totals in front of it itself (block b
+// reads b entries, strided over its threads): no scan launch and no tile of block totals; block 0 also sums all of
+// them and leaves the next level's length and the cut.
+__global__ void __launch_bounds__(SCAN_BLOCK)
+tree_scan_step_kernel(ScanWork w, unsigned level) {
+  __shared__ unsigned wave_tot[SCAN_BLOCK / 64];
+  __shared__ unsigned wave_sum[2][SCAN_BLOCK / 64];
+  if (level > w.hdr->start) return;  // the top kernel has walked this level
+  const unsigned cnt = w.cnt[level];
+  const unsigned b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (b * SCAN_BLOCK >= cnt) return;  // surplus block (cnt == 0: cnt[level - 1] keeps the 0 it was cleared to)
+  const unsigned live_blocks = (cnt + SCAN_BLOCK - 1) / SCAN_BLOCK;
+  const unsigned* tot = w.tot + (size_t)level * w.blocks;
+  unsigned front = 0, all = 0;
+  for (unsigned j = threadIdx.x; j < (b == 0 ? live_blocks : b); j += SCAN_BLOCK) {
+    const unsigned t = tot[j];
+    if (j < b) front += t;
+    all += t;
+  }
+  front = scan_wave_sum(front);
+  all = scan_wave_sum(all);
+  const unsigned i = b * SCAN_BLOCK + threadIdx.x;
+  const bool live = i < cnt;
+  const uint64_t me = live ? w.frontier[level & 1][i] : 0;
+  const unsigned mark = live ? w.marks[level & 1][i] : 0;
+  const unsigned long long bl = __ballot(mark & 1), br = __ballot(mark & 2);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned p = __popcll(bl & below) + __popcll(br & below);
+  if (lane == 0) {
+    wave_tot[wave] = __popcll(bl) + __popcll(br);
+    wave_sum[0][wave] = front;
+    wave_sum[1][wave] = all;
+  }
+  __syncthreads();
+  front = all = 0;
+  for (unsigned v = 0; v < SCAN_BLOCK / 64; ++v) {
+    if (v < wave) p += wave_tot[v];
+    front += wave_sum[0][v];
+    all += wave_sum[1][v];
+  }
+  unsigned wave_first = front;  // position of the wave's first child: its at most 128 children lie in two SCAN_BLOCKs
+  for (unsigned v = 0; v < wave; ++v) wave_first += wave_tot[v];
+  const unsigned bucket = wave_first / SCAN_BLOCK;
+  p += front;
+  const unsigned limit = scan_limit(w, level - 1);
+  uint64_t* next = w.frontier[(level - 1) & 1];
+  unsigned kept_lo = 0, kept_hi = 0;  // kept grandchildren whose parent lies in `bucket` / in the one behind it
+#pragma unroll
+  for (unsigned side = 0; side < 2; ++side) {
+    if (mark & (1u << side)) {
+      if (p < limit) {  // the cut (property 2)
+        const uint64_t child = 2 * me + side;
+        next[p] = child;
+        if (level > 1) {
+          const unsigned m = scan_mark(w, level - 1, child);
+          w.marks[(level - 1) & 1][p] = (uint8_t)m;
+          if (p / SCAN_BLOCK == bucket) kept_lo += (unsigned)__popc(m); else kept_hi += (unsigned)__popc(m);
+        } else {
+          scan_leaf(w, child, p);
+        }
+      }
+      ++p;
+    }
+  }
+  // one atomic per wave and bucket: with one add per child, the 4096 adds of a level went into the ONE cache line
+  // that holds its totals and a 4096-key page took 2.21 ms instead of 0.79
+  kept_lo = scan_wave_sum(kept_lo);
+  kept_hi = scan_wave_sum(kept_hi);
+  if (lane == 0 && level > 1) {
+    unsigned* into = w.tot + (size_t)(level - 1) * w.blocks + bucket;
+    if (kept_lo) atomicAdd(into, kept_lo);
+    if (kept_hi) atomicAdd(into + 1, kept_hi);
+  }
+  if (b == 0 && threadIdx.x == 0) {
+    const unsigned kept = all < limit ? all : limit;
+    if (all > limit) w.hdr->more = 1;
+    if (level > 1) w.cnt[level - 1] = kept; else w.hdr->n = kept;
+  }
+}
+
 struct SparseTree {
   unsigned height = 0;
   uint64_t empty_leaf[4] = {0, 0, 0, 0};
@@ -1273,6 +1536,137 @@ int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, ui
     std::memcpy(leaves, stage + in_bytes, n * 32);
     std::memcpy(siblings, stage + in_bytes + n * 32, pairs * 32);
   }
+  return SP_OK;
+}
+
+// The table's size as it stands: the device counter of claimed slots (read-only) and the slot count.
+int sp_tree_table_size(int tree, uint64_t* entries, uint64_t* slots) {
+  SP_REQUIRE_READY();
+  if (!entries || !slots) { set_error("sp_tree_table_size: null argument"); return SP_ERR_BAD_ARGUMENT; }
+  TreeScope ts;
+  int rc = ts.open(tree);
+  if (rc != SP_OK) return rc;
+  SparseTree& t = *ts.t;
+  unsigned long long used = 0;
+  if (t.d_entries) {
+    SP_HIP(hipMemcpyAsync(&used, t.d_entries, sizeof(used), hipMemcpyDeviceToHost, t.stream));
+    SP_HIP(hipStreamSynchronize(t.stream));
+  }
+  *entries = used;
+  *slots = t.slots;
+  return SP_OK;
+}
+
+// ---- sp_tree_scan (include/starkperp.h): which keys a tree holds, in order, in pages - the descent of
+// tree_scan_top_kernel / tree_scan_step_kernel.  Everything on the tree's stream under the tree's mutex, so a page
+// describes a batch boundary; one wait, at the end. ----
+int sp_tree_scan(int tree, uint64_t lo, uint64_t hi, size_t capacity, uint64_t* keys, uint64_t* leaves, size_t* n,
+                 int* more) {
+  SP_REQUIRE_READY();
+  if (!keys || !leaves || !n || !more) { set_error("sp_tree_scan: null argument"); return SP_ERR_BAD_ARGUMENT; }
+  if (capacity == 0) { set_error("sp_tree_scan: capacity must be at least 1"); return SP_ERR_BAD_ARGUMENT; }
+  if (lo > hi) { set_error("sp_tree_scan: lo above hi"); return SP_ERR_BAD_ARGUMENT; }
+  TimelineScope timeline("sp_tree_scan");
+  TreeScope ts;
+  int rc = ts.open(tree);
+  if (rc != SP_OK) return rc;
+  SparseTree& t = *ts.t;
+  const unsigned height = t.height;
+  if (height < 64 && (hi >> height) != 0) { set_error("sp_tree_scan: hi out of range for height"); return SP_ERR_BAD_ARGUMENT; }
+  if (!t.table || !t.has_root) {  // never updated: no launch
+    *n = 0;
+    *more = 0;
+    return SP_OK;
+  }
+  std::vector<uint64_t> emp;
+  rc = tree_empty_roots(t, emp);
+  if (rc != SP_OK) return rc;
+  if (std::memcmp(t.root, &emp[4 * (size_t)height], 32) == 0) {  // the frontier of level `height` is empty
+    *n = 0;
+    *more = 0;
+    return SP_OK;
+  }
+  const size_t cap = capacity < SP_TREE_SCAN_MAX ? capacity : SP_TREE_SCAN_MAX;
+  const size_t wide = cap + 2;  // what a frontier above level 0 keeps (scan_limit)
+  const size_t blocks = (wide + SCAN_BLOCK - 1) / SCAN_BLOCK;
+  // work buffer: empty roots | header, keys (= frontier 0), leaves: what goes back, one piece | frontier 1 | marks 0 |
+  // marks 1 | cnt[65], tot[height + 1][blocks]: cleared once
+  const size_t emp_bytes = ((size_t)height + 1) * 32, out_bytes = sizeof(ScanHeader) + wide * 8 + cap * 32;
+  const size_t f1_off = emp_bytes + out_bytes, m_off = f1_off + wide * 8, z_off = (m_off + 2 * wide + 15) & ~(size_t)15;
+  const size_t z_bytes = (65 + ((size_t)height + 1) * blocks) * sizeof(unsigned);
+  SP_HIP(t.buf.reserve(z_off + z_bytes + 64));
+  char* b = (char*)t.buf.ptr;
+  ScanWork w;
+  w.tab = t.table;
+  w.mask = t.slots - 1;
+  w.emp = (const uint64_t*)b;
+  w.lo = lo;
+  w.hi = hi;
+  w.cap = (unsigned)cap;
+  w.blocks = (unsigned)blocks;
+  w.hdr = (ScanHeader*)(b + emp_bytes);
+  w.frontier[0] = (uint64_t*)(b + emp_bytes + sizeof(ScanHeader));
+  w.leaves = w.frontier[0] + wide;
+  w.frontier[1] = (uint64_t*)(b + f1_off);
+  w.marks[0] = (uint8_t*)(b + m_off);
+  w.marks[1] = w.marks[0] + wide;
+  w.cnt = (unsigned*)(b + z_off);
+  w.tot = w.cnt + 65;
+  hipStream_t st = t.stream;
+  tl_mark("scan: work buffer ready");
+  // a page up to 4 MiB comes back through the tree's page-locked buffer in one copy; above that the header comes back
+  // first and the n keys and leaves go directly into the caller's arrays
+  char* stage = nullptr;
+  const bool whole = emp_bytes + out_bytes <= PINNED_STAGE_MAX;
+  if (t.hbuf.reserve(whole ? emp_bytes + out_bytes : emp_bytes + sizeof(ScanHeader)) == hipSuccess) stage = (char*)t.hbuf.ptr;
+  else (void)hipGetLastError();
+  if (stage) {
+    std::memcpy(stage, emp.data(), emp_bytes);
+    SP_HIP(hipMemcpyAsync(b, stage, emp_bytes, hipMemcpyHostToDevice, st));
+  } else {
+    SP_HIP(hipMemcpyAsync(b, emp.data(), emp_bytes, hipMemcpyHostToDevice, st));
+  }
+  SP_HIP(hipMemsetAsync(b + z_off, 0, z_bytes, st));
+  hipLaunchKernelGGL(tree_scan_top_kernel, dim3(1), dim3(SCAN_TOP), 0, st, w, height);
+  // The frontier of level height - k has at most 2^k nodes, so the top kernel hands over at level height - 11 or
+  // below, and never when cap + 2 <= SCAN_TOP: those launches are not made.  The others find on the device whether their
+  // level is theirs.
+  if (wide > SCAN_TOP) {
+    for (unsigned level = height > 11 ? height - 11 : 0; level >= 1; --level) {
+      hipLaunchKernelGGL(tree_scan_step_kernel, dim3((unsigned)blocks), dim3(SCAN_BLOCK), 0, st, w, level);
+    }
+  }
+  SP_HIP(hipGetLastError());
+  tl_mark("scan: kernels enqueued");
+  if (timeline.mine) {  // diagnostics only, as in sp_tree_witness
+    SP_HIP(hipStreamSynchronize(st));
+    tl_mark("scan: kernels done");
+  }
+  ScanHeader h;
+  h.n = 0;
+  h.more = 0;
+  h.start = 0;
+  if (stage && whole) {
+    SP_HIP(hipMemcpyAsync(stage + emp_bytes, w.hdr, out_bytes, hipMemcpyDeviceToHost, st));
+    SP_HIP(hipStreamSynchronize(st));
+    std::memcpy(&h, stage + emp_bytes, sizeof(h));
+    if (h.n > cap) { set_error("sp_tree_scan: inconsistent count"); return SP_ERR_HIP; }
+    std::memcpy(keys, stage + emp_bytes + sizeof(h), h.n * 8);
+    std::memcpy(leaves, stage + emp_bytes + sizeof(h) + wide * 8, h.n * 32);
+  } else {
+    SP_HIP(hipMemcpyAsync(stage ? (void*)(stage + emp_bytes) : (void*)&h, w.hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    SP_HIP(hipStreamSynchronize(st));
+    if (stage) std::memcpy(&h, stage + emp_bytes, sizeof(h));
+    if (h.n > cap) { set_error("sp_tree_scan: inconsistent count"); return SP_ERR_HIP; }
+    if (h.n) {
+      SP_HIP(hipMemcpyAsync(keys, w.frontier[0], h.n * 8, hipMemcpyDeviceToHost, st));
+      SP_HIP(hipMemcpyAsync(leaves, w.leaves, h.n * 32, hipMemcpyDeviceToHost, st));
+      SP_HIP(hipStreamSynchronize(st));
+    }
+  }
+  tl_mark("scan: results on the host");
+  *n = (size_t)h.n;
+  *more = h.more ? 1 : 0;
   return SP_OK;
 }
 

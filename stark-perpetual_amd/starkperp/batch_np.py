@@ -367,6 +367,33 @@ def tree_prove(tree, keys):
     return leaves, siblings
 
 
+TREE_SCAN_MAX = 1 << 22  # SP_TREE_SCAN_MAX: the largest page of one sp_tree_scan call
+
+
+def tree_scan(handle, lo, hi, capacity):
+    """One page of the ordered range scan (sp_tree_scan) of the tree behind `handle` (a state.LibrarySparseTree or its
+    integer handle): the first `capacity` keys k, lo <= k <= hi inclusive, whose leaf is not the tree's empty leaf.
+    Returns (keys uint64[n] ascending, leaves uint64[n, 4], more bool); more: further such keys exist in the range,
+    resume with lo = keys[-1] + 1."""
+    handle = getattr(handle, "_handle", handle)
+    cap = min(int(capacity), TREE_SCAN_MAX)
+    keys, leaves = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros((max(cap, 1), 4), dtype=np.uint64)
+    count, more = ctypes.c_size_t(), ctypes.c_int()
+    _lib.check(_lib.ensure_init().sp_tree_scan(handle, lo, hi, capacity, _ptr(keys), _ptr(leaves), ctypes.byref(count),
+                                               ctypes.byref(more)), "sp_tree_scan")
+    return keys[:count.value], leaves[:count.value], bool(more.value)
+
+
+def tree_table_size(handle):
+    """(entries, slots) of the tree's node table as it stands (sp_tree_table_size): slots in use - it never shrinks -
+    and the slot count."""
+    handle = getattr(handle, "_handle", handle)
+    entries, slots = ctypes.c_uint64(), ctypes.c_uint64()
+    _lib.check(_lib.ensure_init().sp_tree_table_size(handle, ctypes.byref(entries), ctypes.byref(slots)),
+               "sp_tree_table_size")
+    return entries.value, slots.value
+
+
 def merkle_verify_update(height, keys, prev_leaves, new_leaves, prev_root, new_root, before, after):
     """The statement of merkle_multi_update(prev_leaves, new_leaves, height, prev_root, new_root)
     (state/state.cairo:155-173) checked against two witnesses in ONE library call (sp_merkle_verify_update): every

@@ -6,7 +6,7 @@
     (services/perpetual/cairo/order/order.cairo:23-59,122-124);
   * tree updates: merkle_multi_update call sites state/state.cairo:155-173.
 All hashing goes through starkperp.batch (GPU)."""
-from typing import Dict, Iterable, List, Sequence, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 from . import batch
 
@@ -187,6 +187,81 @@ class SparseMerkleTree:
             out[i] = node == self.root
         return out
 
+    def scan(self, lo: int = 0, hi: Optional[int] = None, capacity: Optional[int] = None):
+        """Ordered range scan, the host twin of sp_tree_scan: the first `capacity` (None: all) keys k, lo <= k <= hi
+        inclusive (hi None: the last key of the tree), whose leaf differs from the empty leaf, as [(key, leaf)] in
+        ascending order, and `more`: whether further such keys exist in the range.  The same descent as the device's,
+        through the facts store: the frontier of a level holds the nodes whose key interval meets [lo, hi] and whose
+        VALUE differs from the level's empty-subtree root (a leaf set back to the empty leaf leaves nodes that exist
+        but hold empty roots: they are pruned by value), cut after every step to its first capacity + 2 nodes above
+        level 0 and to `capacity` keys at level 0.  The margin of two: a kept node has a live leaf below it, which is
+        in range unless the node's interval sticks out of [lo, hi] - only the first node of a frontier (it holds lo)
+        and the last (it holds hi) can - so a frontier that was cut, and thereby lost its last node, keeps at least
+        capacity + 1 nodes with a leaf in range: the page is complete and a cut at any level means `more`.  No hash."""
+        top = (1 << self.height) - 1
+        hi = top if hi is None else hi
+        assert 0 <= lo <= hi <= top, "scan range out of order or out of range for height"
+        assert capacity is None or capacity >= 1, "capacity must be at least 1"
+        more = False
+        frontier = [(0, self.root)] if self.root != self.empties[self.height] else []
+        for level in range(self.height, 0, -1):
+            below = []
+            for idx, node in frontier:
+                for child, value in zip((2 * idx, 2 * idx + 1), self._children(node, level)):
+                    first = child << (level - 1)
+                    if value != self.empties[level - 1] and first <= hi and first | ((1 << (level - 1)) - 1) >= lo:
+                        below.append((child, value))
+            limit = None if capacity is None else capacity + 2 if level > 1 else capacity
+            if limit is not None and len(below) > limit:
+                more, below = True, below[:limit]
+            frontier = below
+        return frontier, more
+
+    def items(self, lo: int = 0, hi: Optional[int] = None, page: int = 65536):
+        """Generator over every (key, leaf) of `scan`'s range, one scan of `page` keys at a time."""
+        return _scan_pages(self, lo, hi, page)
+
+    def snapshot(self) -> dict:
+        """Everything that defines the tree: {"height", "empty_leaf", "root", "keys", "leaves"} (lists of ints, the keys
+        ascending).  `restore` rebuilds an equal tree from it."""
+        pairs = list(self.items())
+        return {"height": self.height, "empty_leaf": self.empties[0], "root": self.root,
+                "keys": [k for k, _ in pairs], "leaves": [v for _, v in pairs]}
+
+    @classmethod
+    def restore(cls, snapshot: dict, hash_many=None, chunk: int = 1 << 18) -> "SparseMerkleTree":
+        """A fresh tree holding the snapshot's leaves, written in ascending chunks; ValueError when the root that
+        results is not the snapshot's."""
+        tree = cls(int(snapshot["height"]), int(snapshot["empty_leaf"]), hash_many)
+        keys, leaves = _snapshot_ints(snapshot)
+        for at in range(0, len(keys), chunk):
+            tree.update(dict(zip(keys[at:at + chunk], leaves[at:at + chunk])))
+        if tree.root != int(snapshot["root"]):
+            raise ValueError("the restored tree's root is not the snapshot's")
+        return tree
+
+
+def _scan_pages(tree, lo, hi, page):
+    """The pages of tree.scan(lo, hi, page) one after the other: `more` says whether to go on, the next page starts
+    behind the last key (which is below hi whenever more is set)."""
+    while True:
+        pairs, more = tree.scan(lo, hi, page)
+        yield from pairs
+        if not more:
+            return
+        lo = pairs[-1][0] + 1
+
+
+def _snapshot_ints(snapshot):
+    """(keys, leaves) of a snapshot as lists of ints, whichever class took it (arrays or lists)."""
+    keys, leaves = snapshot["keys"], snapshot["leaves"]
+    if hasattr(keys, "tolist"):
+        keys = keys.tolist()
+    if hasattr(leaves, "shape"):
+        from . import batch_np
+        leaves = batch_np.ints_from_felts(leaves) if len(keys) else []
+    return [int(k) for k in keys], [int(v) for v in leaves]
+
 
 def facts_of(witness) -> Dict[int, Tuple[int, int]]:
     """Witness records -> {node: (left, right)}: the shape of program_input['merkle_facts'] (main.cairo:39-40)."""
@@ -357,6 +432,8 @@ class LibrarySparseTree:
         from . import _lib
         self._lib, self._ct = _lib, ctypes
         self.height = height
+        self.empty_leaf = empty_leaf
+        self.context = context
         handle = ctypes.c_int()
         _lib.check(_lib.ensure_init().sp_tree_create_on(context, height, _lib.pack_felts([empty_leaf]),
                                                         ctypes.byref(handle)), "sp_tree_create_on")
@@ -476,6 +553,75 @@ class LibrarySparseTree:
         for i, ok in zip(good, verdict.tolist()):
             out[i] = ok
         return out
+
+    def scan(self, lo: int = 0, hi: Optional[int] = None, capacity: Optional[int] = None):
+        """As SparseMerkleTree.scan, one page in one call (sp_tree_scan): ([(key, leaf)] ascending, more).  capacity
+        None: the largest page of a call (batch_np.TREE_SCAN_MAX keys); `items` pages through any number."""
+        from . import batch_np
+        top = (1 << self.height) - 1
+        hi = top if hi is None else hi
+        assert 0 <= lo <= hi <= top, "scan range out of order or out of range for height"
+        assert capacity is None or capacity >= 1, "capacity must be at least 1"
+        keys, leaves, more = batch_np.tree_scan(self, lo, hi, batch_np.TREE_SCAN_MAX if capacity is None else capacity)
+        return list(zip(keys.tolist(), batch_np.ints_from_felts(leaves))), more
+
+    def items(self, lo: int = 0, hi: Optional[int] = None, page: int = 65536):
+        """Generator over every (key, leaf) of `scan`'s range, one sp_tree_scan call of `page` keys at a time.  Each
+        page describes a batch boundary (the tree's mutex); an update between two pages shows in the later ones."""
+        return _scan_pages(self, lo, hi, page)
+
+    def snapshot(self, page: int = 1 << 18) -> dict:
+        """Everything that defines the tree: {"height", "empty_leaf", "root", "keys" uint64[n] ascending, "leaves"
+        uint64[n, 4]}, read in pages of `page` keys.  The caller keeps updates away while it is taken; the root is read
+        first and `restore` compares it, so a snapshot torn by an update does not restore."""
+        import numpy as np
+        from . import batch_np
+        root, lo, top = self.root, 0, (1 << self.height) - 1
+        keys, leaves = [np.zeros(0, dtype=np.uint64)], [np.zeros((0, 4), dtype=np.uint64)]
+        while True:
+            k, v, more = batch_np.tree_scan(self, lo, top, page)
+            keys.append(k)
+            leaves.append(v)
+            if not more:
+                break
+            lo = int(k[-1]) + 1
+        return {"height": self.height, "empty_leaf": self.empty_leaf, "root": root,
+                "keys": np.concatenate(keys), "leaves": np.concatenate(leaves)}
+
+    @classmethod
+    def restore(cls, snapshot: dict, context: int = 0, chunk: int = 1 << 18) -> "LibrarySparseTree":
+        """A fresh tree on `context` that holds the snapshot's leaves (of either tree class): the keys go to
+        `update_arrays` in ascending chunks of `chunk`; ValueError, with the new tree closed, when the root that
+        results is not the snapshot's.  Saving, moving to another context and compacting are all this."""
+        import numpy as np
+        from . import batch_np
+        keys, leaves = snapshot["keys"], snapshot["leaves"]
+        if not hasattr(leaves, "shape"):
+            leaves = batch_np.felts_from_ints(leaves) if len(leaves) else np.zeros((0, 4), dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        tree = cls(int(snapshot["height"]), int(snapshot["empty_leaf"]), context)
+        try:
+            assert keys.ndim == 1 and leaves.shape == (keys.shape[0], 4) and (keys[1:] > keys[:-1]).all(), \
+                "snapshot keys must be strictly increasing, one leaf each"
+            for at in range(0, keys.shape[0], chunk):
+                tree.update_arrays(keys[at:at + chunk], leaves[at:at + chunk])
+            if tree.root != int(snapshot["root"]):
+                raise ValueError("the restored tree's root is not the snapshot's")
+        except BaseException:
+            tree.close()
+            raise
+        return tree
+
+    def compacted(self) -> "LibrarySparseTree":
+        """A new tree with the same leaves and a table that holds only what they need (the table of a live tree only
+        grows, and keeps the paths of leaves that were set back to the empty leaf)."""
+        return self.restore(self.snapshot(), context=self.context)
+
+    @property
+    def entries(self) -> int:
+        """Slots of the node table in use (sp_tree_table_size): it never shrinks."""
+        from . import batch_np
+        return batch_np.tree_table_size(self)[0]
 
     def close(self):
         if self._handle is not None:
@@ -667,6 +813,32 @@ class SharedState:
             self.positions.update({k: hv for (k, _, _), hv in zip(pos, prev_h)})
             raise
         return pos_roots, ord_roots
+
+    def snapshot(self) -> dict:
+        """{"positions": ..., "orders": ...}: the `snapshot` of both trees, taken between two batches."""
+        return {"positions": self.positions.snapshot(), "orders": self.orders.snapshot()}
+
+    @classmethod
+    def restore(cls, snap: dict, hash_many=None, position_hashes=None, context: int = 0) -> "SharedState":
+        """A state whose two trees are restored from `snap` (SharedState.snapshot of either route): library trees on
+        `context` when hash_many is None, host twins on the injected hash otherwise.  ValueError when a tree does not
+        come back to its snapshot's root; nothing is left open then."""
+        out = cls(int(snap["positions"]["height"]), int(snap["orders"]["height"]), hash_many, position_hashes)
+        out.close()  # the empty trees of __init__ give way to the restored ones
+        trees = []
+        try:
+            for part in ("positions", "orders"):
+                if hash_many is None:
+                    trees.append(LibrarySparseTree.restore(snap[part], context=context))
+                else:
+                    trees.append(SparseMerkleTree.restore(snap[part], hash_many))
+        except BaseException:
+            for tree in trees:
+                if hasattr(tree, "close"):
+                    tree.close()
+            raise
+        out.positions, out.orders = trees
+        return out
 
     def close(self):
         """Releases the library-side trees (no-op for the host-bookkeeping variant)."""
