@@ -3,7 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <condition_variable>
+#include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <utility>
 #include <string>
@@ -76,6 +78,99 @@ struct PinnedBuffer {
   void release() {
     if (ptr) (void)hipHostFree(ptr);
     ptr = nullptr;
+    bytes = 0;
+  }
+};
+
+// One host array of a staged round trip.  A null `ptr` keeps its `bytes` in the layout and is copied in neither branch:
+// an output the caller did not ask for, or padding between two device arrays.
+struct Piece {
+  void* ptr;
+  size_t bytes;
+  Piece(const void* p, size_t b) : ptr(const_cast<void*>(p)), bytes(b) {}
+};
+// The round trip of a host-pointer call whose inputs are adjacent on the device and whose outputs are too.  The
+// constructor makes the PinnedBuffer decision for `bytes` (inputs + outputs) - the only place that does:
+//   stage != nullptr   STAGED: the pieces share one page-locked block, inputs first, and cross in one copy each way;
+//   stage == nullptr   DIRECT: one copy per piece, from / into the caller's arrays (a batch above PINNED_STAGE_MAX, or
+//                      a page-locked allocation that failed - its error is cleared here).
+// up() before the kernels, down() behind them, finish() after the caller's own wait on the stream.  A call whose copies
+// have another shape (tree_enqueue, the large page of sp_tree_scan, ecdsa.hip stage_in_lane) reads `stage` and copies
+// for itself.
+struct StagedTrip {
+  char* stage = nullptr;
+  hipStream_t st;
+  size_t up_bytes = 0;  // where the outputs start in the block
+  static bool fits(size_t bytes) { return bytes <= PINNED_STAGE_MAX; }
+  StagedTrip(PinnedBuffer& buf, size_t bytes, hipStream_t stream) : st(stream) {
+    if (fits(bytes) && buf.reserve(bytes) == hipSuccess) stage = (char*)buf.ptr;
+    else (void)hipGetLastError();
+  }
+  // the host pieces -> dev, one behind the other
+  hipError_t up(void* dev, std::initializer_list<Piece> pieces) {
+    size_t at = 0;
+    for (const Piece& p : pieces) {
+      if (p.ptr && stage) std::memcpy(stage + at, p.ptr, p.bytes);
+      if (p.ptr && !stage) {
+        const hipError_t e = hipMemcpyAsync((char*)dev + at, p.ptr, p.bytes, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+      }
+      at += p.bytes;
+    }
+    up_bytes = at;
+    return stage ? hipMemcpyAsync(dev, stage, at, hipMemcpyHostToDevice, st) : hipSuccess;
+  }
+  // dev, one piece behind the other -> the block (staged) or the host pieces (direct); enqueued only
+  hipError_t down(const void* dev, std::initializer_list<Piece> pieces) {
+    size_t at = 0;
+    for (const Piece& p : pieces) {
+      if (p.ptr && !stage) {
+        const hipError_t e = hipMemcpyAsync(p.ptr, (const char*)dev + at, p.bytes, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return e;
+      }
+      at += p.bytes;
+    }
+    return stage ? hipMemcpyAsync(stage + up_bytes, dev, at, hipMemcpyDeviceToHost, st) : hipSuccess;
+  }
+  // after the wait: the block -> the host pieces (direct: they are there already)
+  void finish(std::initializer_list<Piece> pieces) const {
+    size_t at = up_bytes;
+    for (const Piece& p : pieces) {
+      if (p.ptr && stage) std::memcpy(p.ptr, stage + at, p.bytes);
+      at += p.bytes;
+    }
+  }
+};
+
+// Device memory that grows without a device-wide wait: hipFree synchronises the whole device (in sp_order_batch it
+// stalled the verification running beside a tree update), so the allocation a growth replaces is RETIRED, not freed -
+// work already on the stream may still read it, and grow() hands it back for the caller's own copy or rehash out of
+// it.  It is freed at the next growth, behind a wait for the one stream, or by release().  Sizing is the caller's.
+template <class T>
+struct RetiringBuffer {
+  T* ptr = nullptr;
+  T* retired = nullptr;
+  size_t bytes = 0;
+  hipError_t grow(size_t want, hipStream_t st, T** old = nullptr) {
+    if (retired) {  // the allocation before the last one: only work older than the last growth can still read it
+      const hipError_t e = hipStreamSynchronize(st);
+      if (e != hipSuccess) return e;
+      (void)hipFree(retired);
+      retired = nullptr;
+    }
+    T* fresh = nullptr;
+    const hipError_t e = hipMalloc(&fresh, want);
+    if (e != hipSuccess) return e;
+    retired = ptr;
+    ptr = fresh;
+    bytes = want;
+    if (old) *old = retired;
+    return hipSuccess;
+  }
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    if (retired) (void)hipFree(retired);
+    ptr = retired = nullptr;
     bytes = 0;
   }
 };

@@ -1053,9 +1053,7 @@ static int stage_in_lane(HostLane& L, const uint64_t* const* host, int count, si
   char* base = (char*)L.io.ptr;
   // small batches go through the lane's page-locked buffer (one host memcpy per input, then asynchronous DMA); a
   // failed page-locked allocation just keeps the direct copies
-  char* stage = nullptr;
-  if ((size_t)count * fb <= PINNED_STAGE_MAX && L.hio.reserve((size_t)count * fb) == hipSuccess) stage = (char*)L.hio.ptr;
-  else (void)hipGetLastError();
+  char* const stage = StagedTrip(L.hio, (size_t)count * fb, L.stream).stage;
   for (int i = 0; i < count; ++i) {
     if (host[i]) {
       dev[i] = (uint64_t*)(base + (size_t)i * fb);

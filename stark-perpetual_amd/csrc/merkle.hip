@@ -29,29 +29,14 @@ static DeviceBuffer g_sparse_buf;
 // empty-subtree roots are a pure function of the empty leaf: cached on the host per leaf value
 static std::map<std::vector<uint64_t>, std::vector<uint64_t>> g_empty_cache;  // leaf -> 65 felts
 // Work buffer of sp_merkle_verify_update[_dev], one per stream like the hash scratch: roots | node indices | child lists
-// | hashes | their status bytes.  It grows the way a tree's slot table does (tree_reserve): the old allocation is
-// RETIRED, not freed - hipFree waits for the whole device - and goes back at the next growth, behind a wait for the
-// stream alone.  `host` stages keys and roots (page-locked, so a _dev call has consumed both when it returns); `copied`
-// marks the last copy out of it and is waited for before it is written again (RaggedStage of pedersen.hip).
-struct VerifyWork {
-  void* ptr = nullptr;
-  void* retired = nullptr;
-  size_t bytes = 0;
-  PinnedBuffer host;
-  hipEvent_t copied = nullptr;
-  bool pending = false;
-};
+// | hashes | their status bytes.  It grows as a tree's slot table does (RetiringBuffer of context.hpp); keys and roots
+// reach it through the stream's page-locked buffer (stage_copy of pedersen.hpp).
+using VerifyWork = RetiringBuffer<char>;
 static std::map<StreamKey, VerifyWork> g_verify_work;
 void release_merkle_state() {
   g_sparse_buf.release();
   g_empty_cache.clear();
-  for (auto& kv : g_verify_work) {
-    VerifyWork& w = kv.second;
-    if (w.ptr) (void)hipFree(w.ptr);
-    if (w.retired) (void)hipFree(w.retired);
-    if (w.copied) (void)hipEventDestroy(w.copied);
-    w.host.release();
-  }
+  for (auto& kv : g_verify_work) kv.second.release();
   g_verify_work.clear();
 }
 
@@ -66,6 +51,16 @@ static bool felt_below_p(const uint64_t* v) {
     if (v[i] != P[i]) return v[i] < P[i];
   }
   return false;
+}
+
+// The one key check: every key below 2^height and, where the call walks the keys' induced subtree (`ordered`), the keys
+// strictly increasing.  false: the text is in sp_last_error.
+static bool keys_ok(unsigned height, const uint64_t* keys, size_t n, bool ordered) {
+  for (size_t i = 0; i < n; ++i) {
+    if (ordered && i > 0 && keys[i] <= keys[i - 1]) { set_error("keys must be strictly increasing"); return false; }
+    if (height < 64 && (keys[i] >> height) != 0) { set_error("key out of range for height"); return false; }
+  }
+  return true;
 }
 
 // empty-subtree roots: empties[k+1] = H(empties[k], empties[k]); 64 sequential hashes the first
@@ -98,10 +93,7 @@ extern "C" int sp_merkle_sparse_root(const uint64_t* keys, const uint64_t* leave
   SP_REQUIRE_READY();
   if (height > 64) { set_error("height must be <= 64"); return SP_ERR_BAD_ARGUMENT; }
   if (!felt_below_p(empty_leaf)) { set_error("empty leaf must be a field element (< p)"); return SP_ERR_BAD_ARGUMENT; }
-  for (size_t i = 0; i < n; ++i) {
-    if (i > 0 && keys[i] <= keys[i - 1]) { set_error("keys must be strictly increasing"); return SP_ERR_BAD_ARGUMENT; }
-    if (height < 64 && (keys[i] >> height) != 0) { set_error("key out of range for height"); return SP_ERR_BAD_ARGUMENT; }
-  }
+  if (!keys_ok(height, keys, n, true)) return SP_ERR_BAD_ARGUMENT;
   Context& c = ctx();
   ctx_lock lk(c.mu);
   // ---- host bookkeeping: induced subtree (merkle_tree.py:18-26) ----
@@ -836,8 +828,7 @@ struct SparseTree {
   unsigned height = 0;
   uint64_t empty_leaf[4] = {0, 0, 0, 0};
   int ctx_index = 0;           // the context (device) the tree lives on
-  TreeSlot* table = nullptr;   // HBM
-  TreeSlot* retired = nullptr; // the table before the last growth (tree_reserve), freed at the next growth / with the tree
+  RetiringBuffer<TreeSlot> table;  // HBM; the table before the last growth (tree_reserve) stays until the next one
   uint64_t slots = 0;          // power of two
   uint64_t entries = 0;        // used slots as of the last read of d_entries
   unsigned long long* d_entries = nullptr;  // device counter of claimed slots (insert kernels add to it)
@@ -868,15 +859,13 @@ static void tree_free(SparseTree& t) {
     (void)hipStreamSynchronize(t.stream);
     (void)hipStreamDestroy(t.stream);
   }
-  if (t.table) (void)hipFree(t.table);
-  if (t.retired) (void)hipFree(t.retired);
+  t.table.release();
   if (t.d_entries) (void)hipFree(t.d_entries);
   t.buf.release();
   t.hbuf.release();
   t.cpts.release();
   t.cpts_state = 0;
   t.stream = nullptr;
-  t.table = t.retired = nullptr;
   t.d_entries = nullptr;
   t.slots = 0;
 }
@@ -913,11 +902,10 @@ struct TreeScope {
 // Room for `extra` more entries at a load factor of at most 1/2 (tree mutex held).
 // Growth policy (round 6): a table that has to grow is sized for FOUR times what is asked of it
 // (load factor 1/4 straight after a growth), so that the next updates of the same size fit without another one, and
-// the growth itself costs the caller no wait: allocation, clear and rehash are enqueued on the tree's stream and the
-// old table is retired, not freed - hipFree synchronises the whole device, which in sp_order_batch stalled the
-// verification running beside the update (calls 1 - 2 of a fresh tree cost 2.9 - 3.1 ms against 1.97 ms in round
-// 5).  The retired table goes back at the next growth (its rehash has long finished: the intervening update
-// synchronised the stream) or with the tree.  First allocation: 2^16 slots, or STARKPERP_TREE_INITIAL_SLOTS_LOG2.
+// the growth itself costs the caller no wait: clear and rehash are enqueued on the tree's stream and the old table is
+// retired, not freed (RetiringBuffer of context.hpp: with a hipFree, calls 1 - 2 of a fresh tree cost 2.9 - 3.1 ms
+// against 1.97 ms in round 5).  By the next growth its rehash has long finished: the intervening update synchronised
+// the stream.  First allocation: 2^16 slots, or STARKPERP_TREE_INITIAL_SLOTS_LOG2.
 static uint64_t tree_initial_slots() {
   static const uint64_t v = [] {
     const char* e = getenv("STARKPERP_TREE_INITIAL_SLOTS_LOG2");
@@ -941,23 +929,29 @@ static int tree_reserve(SparseTree& t, uint64_t extra) {
   uint64_t want = t.slots ? t.slots : tree_initial_slots();
   while (4 * (t.entries + extra) > want) want <<= 1;
   if (want == t.slots) return SP_OK;
-  if (t.retired) {  // the table before the last one: nothing on the stream reads it any more
-    SP_HIP(hipStreamSynchronize(t.stream));
-    (void)hipFree(t.retired);
-    t.retired = nullptr;
-  }
-  TreeSlot* fresh = nullptr;
-  SP_HIP(hipMalloc(&fresh, want * sizeof(TreeSlot)));
+  TreeSlot* old = nullptr;
+  SP_HIP(t.table.grow(want * sizeof(TreeSlot), t.stream, &old));
   tl_mark("tree: table allocated");
-  SP_HIP(hipMemsetAsync(fresh, 0, want * sizeof(TreeSlot), t.stream));
-  if (t.table) {
-    hipLaunchKernelGGL(tree_rehash_kernel, dim3((unsigned)((t.slots + 255) / 256)), dim3(256), 0, t.stream, t.table,
-                       t.slots, fresh, want - 1);
+  SP_HIP(hipMemsetAsync(t.table.ptr, 0, want * sizeof(TreeSlot), t.stream));
+  if (old) {
+    hipLaunchKernelGGL(tree_rehash_kernel, dim3((unsigned)((t.slots + 255) / 256)), dim3(256), 0, t.stream, old, t.slots,
+                       t.table.ptr, want - 1);
     SP_HIP(hipGetLastError());
-    t.retired = t.table;  // read by the rehash just enqueued; freed later, without a device-wide wait now
   }
-  t.table = fresh;
   t.slots = want;
+  return SP_OK;
+}
+
+// The empty-subtree roots of the tree's levels, a copy (tree mutex held; the cache and the scratch map are shared).
+static int tree_empty_roots(const SparseTree& t, std::vector<uint64_t>& out) {
+  ctx_lock lk(global_mu());
+  Scratch s;
+  int rc = get_scratch_public(1, s, 0);
+  if (rc != SP_OK) return rc;
+  const std::vector<uint64_t>* emp = nullptr;
+  rc = empty_roots(t.empty_leaf, s, &emp);
+  if (rc != SP_OK) return rc;
+  out.assign(emp->begin(), emp->begin() + 4 * ((size_t)t.height + 1));
   return SP_OK;
 }
 
@@ -966,14 +960,10 @@ static int tree_root_locked(SparseTree& t, uint64_t* root) {
     std::memcpy(root, t.root, 32);
     return SP_OK;
   }
-  ctx_lock lk(global_mu());  // the cache of empty-subtree roots and the scratch map are shared
-  Scratch s;
-  int rc = get_scratch_public(1, s, 0);
+  std::vector<uint64_t> emp;
+  const int rc = tree_empty_roots(t, emp);
   if (rc != SP_OK) return rc;
-  const std::vector<uint64_t>* emp = nullptr;
-  rc = empty_roots(t.empty_leaf, s, &emp);
-  if (rc != SP_OK) return rc;
-  std::memcpy(root, emp->data() + 4 * t.height, 32);
+  std::memcpy(root, &emp[4 * (size_t)t.height], 32);
   return SP_OK;
 }
 
@@ -1009,14 +999,6 @@ struct TreePending {  // what tree_enqueue leaves for tree_wait / tree_commit
   unsigned flag_host = 0;             // ... these, for an update too large for it
   uint64_t root_host[4] = {0, 0, 0, 0};
 };
-
-static bool tree_keys_ok(const SparseTree& t, const uint64_t* keys, size_t n) {
-  for (size_t i = 0; i < n; ++i) {
-    if (i > 0 && keys[i] <= keys[i - 1]) { set_error("keys must be strictly increasing"); return false; }
-    if (t.height < 64 && (keys[i] >> t.height) != 0) { set_error("key out of range for height"); return false; }
-  }
-  return true;
-}
 
 // ---- host: only the node COUNT of every level (merkle_tree.py:18-26 on the keys alone): level l has one node
 // per distinct key >> l, i.e. 1 + the adjacent key pairs whose highest differing bit is >= l.  keys sorted, n >= 1;
@@ -1063,7 +1045,7 @@ static int tree_enqueue(SparseTree& t, const uint64_t* keys, const uint64_t* lea
                         uint8_t* status, const LeafProducer* producer, TreePending& p,
                         const std::function<void()>* enqueued = nullptr) {
   const unsigned height = t.height;
-  if (!tree_keys_ok(t, keys, n)) return SP_ERR_BAD_ARGUMENT;
+  if (!keys_ok(height, keys, n, true)) return SP_ERR_BAD_ARGUMENT;
   int rc = tree_root_locked(t, old_root);
   if (rc != SP_OK) return rc;
   if (status) *status = 0;
@@ -1101,9 +1083,7 @@ static int tree_enqueue(SparseTree& t, const uint64_t* keys, const uint64_t* lea
     const size_t leaf_bytes = leaves ? n * 32 : 0;
     const size_t land_off = (emp_bytes + leaf_bytes + n * 8 + 31) & ~(size_t)31;
     const size_t in_bytes = land_off + 64 + (producer ? producer->host_bytes : 0);
-    char* stage = nullptr;
-    if (in_bytes <= PINNED_STAGE_MAX && t.hbuf.reserve(in_bytes) == hipSuccess) stage = (char*)t.hbuf.ptr;
-    else (void)hipGetLastError();
+    char* const stage = StagedTrip(t.hbuf, in_bytes, st).stage;  // the decision only: the copies below are its own
     if (stage) {
       h_flag = (unsigned*)(stage + land_off);
       h_root = (uint64_t*)(stage + land_off + 32);
@@ -1139,7 +1119,7 @@ static int tree_enqueue(SparseTree& t, const uint64_t* keys, const uint64_t* lea
     }
     tl_mark("tree: inputs copied");
     if (producer && producer->place) {  // level 0 comes from (or is checked by) a kernel on this stream
-      rc = producer->place(b + prod_off, prod_host, t.table, t.slots - 1, d_idx, d_emp, d_felts, s.flag, st);
+      rc = producer->place(b + prod_off, prod_host, t.table.ptr, t.slots - 1, d_idx, d_emp, d_felts, s.flag, st);
       if (rc != SP_OK) return rc;
       tl_mark("tree: leaf kernel enqueued");
     }
@@ -1147,7 +1127,7 @@ static int tree_enqueue(SparseTree& t, const uint64_t* keys, const uint64_t* lea
     hipLaunchKernelGGL(tree_level_nodes_kernel, dim3(height), dim3(1024), 0, st, lv, d_idx, d_idx);
     hipLaunchKernelGGL(tree_children_kernel, dim3((unsigned)((total - cnt[height] + 255) / 256)), dim3(256), 0, st, lv,
                        d_idx, d_src, (unsigned)(total - cnt[height]));
-    hipLaunchKernelGGL(tree_lookup_kernel, dim3((unsigned)((srcs + 255) / 256)), dim3(256), 0, st, lv, d_idx, t.table,
+    hipLaunchKernelGGL(tree_lookup_kernel, dim3((unsigned)((srcs + 255) / 256)), dim3(256), 0, st, lv, d_idx, t.table.ptr,
                        t.slots - 1, d_felts, d_src, (unsigned)srcs);
     SP_HIP(hipGetLastError());
     tl_mark("tree: structure kernels enqueued");
@@ -1211,7 +1191,7 @@ static int tree_wait(SparseTree& t, const TreePending& p, unsigned* flag) {
 // buffer, the rehash of a growing table); a reallocation of the work buffer or sp_tree_destroy synchronise
 // (hipFree / tree_free).  ~0.09 ms of 217 k hash-table insertions leave the caller's latency.
 static int tree_commit(SparseTree& t, const TreePending& p, uint64_t* new_root) {
-  hipLaunchKernelGGL(tree_insert_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, t.stream, t.table,
+  hipLaunchKernelGGL(tree_insert_kernel, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, t.stream, t.table.ptr,
                      t.slots - 1, p.lv, p.d_idx, p.d_felts, (unsigned)p.total, t.d_entries);
   SP_HIP(hipGetLastError());
   std::memcpy(t.root, p.h_root, 32);
@@ -1316,11 +1296,9 @@ int sp_tree_get(int tree, const uint64_t* keys, size_t n, uint64_t* leaves) {
   int rc = ts.open(tree);
   if (rc != SP_OK) return rc;
   SparseTree& t = *ts.t;
-  for (size_t i = 0; i < n; ++i) {
-    if (t.height < 64 && (keys[i] >> t.height) != 0) { set_error("key out of range for height"); return SP_ERR_BAD_ARGUMENT; }
-  }
+  if (!keys_ok(t.height, keys, n, false)) return SP_ERR_BAD_ARGUMENT;
   if (n == 0) return SP_OK;
-  if (!t.table) {
+  if (!t.table.ptr) {
     for (size_t i = 0; i < n; ++i) std::memcpy(leaves + 4 * i, t.empty_leaf, 32);
     return SP_OK;
   }
@@ -1331,7 +1309,7 @@ int sp_tree_get(int tree, const uint64_t* keys, size_t n, uint64_t* leaves) {
   uint64_t* d_out = d_emp + 4;
   SP_HIP(hipMemcpyAsync(d_keys, keys, n * 8, hipMemcpyHostToDevice, t.stream));
   SP_HIP(hipMemcpyAsync(d_emp, t.empty_leaf, 32, hipMemcpyHostToDevice, t.stream));
-  hipLaunchKernelGGL(tree_get_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t.stream, t.table, t.slots - 1,
+  hipLaunchKernelGGL(tree_get_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t.stream, t.table.ptr, t.slots - 1,
                      d_keys, (unsigned)n, d_emp, d_out);
   SP_HIP(hipGetLastError());
   SP_HIP(hipMemcpyAsync(leaves, d_out, n * 32, hipMemcpyDeviceToHost, t.stream));
@@ -1344,10 +1322,7 @@ int sp_tree_get(int tree, const uint64_t* keys, size_t n, uint64_t* leaves) {
 int sp_tree_witness_size(unsigned height, const uint64_t* keys, size_t n, size_t* n_records) {
   if (!n_records || (n && !keys)) { set_error("sp_tree_witness_size: null argument"); return SP_ERR_BAD_ARGUMENT; }
   if (height < 1 || height > 64) { set_error("height must be in 1..64"); return SP_ERR_BAD_ARGUMENT; }
-  for (size_t i = 0; i < n; ++i) {
-    if (i > 0 && keys[i] <= keys[i - 1]) { set_error("keys must be strictly increasing"); return SP_ERR_BAD_ARGUMENT; }
-    if (height < 64 && (keys[i] >> height) != 0) { set_error("key out of range for height"); return SP_ERR_BAD_ARGUMENT; }
-  }
+  if (!keys_ok(height, keys, n, true)) return SP_ERR_BAD_ARGUMENT;
   size_t records = 0;
   if (n) {
     std::vector<size_t> cnt;
@@ -1355,19 +1330,6 @@ int sp_tree_witness_size(unsigned height, const uint64_t* keys, size_t n, size_t
     for (unsigned l = 1; l <= height; ++l) records += cnt[l];
   }
   *n_records = records;
-  return SP_OK;
-}
-
-// The empty-subtree roots of the tree's levels, a copy (tree mutex held; the cache and the scratch map are shared).
-static int tree_empty_roots(const SparseTree& t, std::vector<uint64_t>& out) {
-  ctx_lock lk(global_mu());
-  Scratch s;
-  int rc = get_scratch_public(1, s, 0);
-  if (rc != SP_OK) return rc;
-  const std::vector<uint64_t>* emp = nullptr;
-  rc = empty_roots(t.empty_leaf, s, &emp);
-  if (rc != SP_OK) return rc;
-  out.assign(emp->begin(), emp->begin() + 4 * ((size_t)t.height + 1));
   return SP_OK;
 }
 
@@ -1381,7 +1343,7 @@ int sp_tree_witness(int tree, const uint64_t* keys, size_t n, size_t capacity, u
   if (rc != SP_OK) return rc;
   SparseTree& t = *ts.t;
   const unsigned height = t.height;
-  if (!tree_keys_ok(t, keys, n)) return SP_ERR_BAD_ARGUMENT;
+  if (!keys_ok(height, keys, n, true)) return SP_ERR_BAD_ARGUMENT;
   if (n == 0) { *n_records = 0; return SP_OK; }
   std::vector<size_t> cnt;
   TreeLevels lv;
@@ -1394,7 +1356,7 @@ int sp_tree_witness(int tree, const uint64_t* keys, size_t n, size_t capacity, u
   std::vector<uint64_t> emp;
   rc = tree_empty_roots(t, emp);
   if (rc != SP_OK) return rc;
-  if (!t.table) {  // never updated: every position is its level's empty-subtree root; the indices as the kernel finds them
+  if (!t.table.ptr) {  // never updated: every position is its level's empty-subtree root; the indices as the kernel finds them
     size_t u = 0;
     for (unsigned l = 1; l <= height; ++l) {
       for (size_t i = 0; i < n; ++i) {
@@ -1424,19 +1386,10 @@ int sp_tree_witness(int tree, const uint64_t* keys, size_t n, size_t capacity, u
   tl_mark("witness: work buffer ready");
   // small results through the tree's page-locked buffer (its previous user has finished: every operation ends with a
   // wait on the stream), larger ones directly into the caller's arrays
-  char* stage = nullptr;
-  if (in_bytes + out_bytes <= PINNED_STAGE_MAX && t.hbuf.reserve(in_bytes + out_bytes) == hipSuccess) stage = (char*)t.hbuf.ptr;
-  else (void)hipGetLastError();
-  if (stage) {
-    std::memcpy(stage, emp.data(), emp_bytes);
-    std::memcpy(stage + emp_bytes, keys, n * 8);
-    SP_HIP(hipMemcpyAsync(d_emp, stage, in_bytes, hipMemcpyHostToDevice, st));
-  } else {
-    SP_HIP(hipMemcpyAsync(d_emp, emp.data(), emp_bytes, hipMemcpyHostToDevice, st));
-    SP_HIP(hipMemcpyAsync(d_idx, keys, n * 8, hipMemcpyHostToDevice, st));
-  }
+  StagedTrip trip(t.hbuf, in_bytes + out_bytes, st);
+  SP_HIP(trip.up(d_emp, {{emp.data(), emp_bytes}, {keys, n * 8}}));
   hipLaunchKernelGGL(tree_level_nodes_kernel, dim3(height), dim3(1024), 0, st, lv, d_idx, d_idx);
-  hipLaunchKernelGGL(tree_witness_kernel, dim3((unsigned)((records + 255) / 256)), dim3(256), 0, st, lv, d_idx, t.table,
+  hipLaunchKernelGGL(tree_witness_kernel, dim3((unsigned)((records + 255) / 256)), dim3(256), 0, st, lv, d_idx, t.table.ptr,
                      t.slots - 1, d_emp, d_node, d_left, d_right, (unsigned)records);
   SP_HIP(hipGetLastError());
   tl_mark("witness: kernels enqueued");
@@ -1444,23 +1397,12 @@ int sp_tree_witness(int tree, const uint64_t* keys, size_t n, size_t capacity, u
     SP_HIP(hipStreamSynchronize(st));
     tl_mark("witness: kernels done");
   }
-  if (stage) {
-    SP_HIP(hipMemcpyAsync(stage + in_bytes, d_idx + n, out_bytes, hipMemcpyDeviceToHost, st));
-  } else {
-    SP_HIP(hipMemcpyAsync(index, d_idx + n, records * 8, hipMemcpyDeviceToHost, st));
-    SP_HIP(hipMemcpyAsync(node, d_node, records * 32, hipMemcpyDeviceToHost, st));
-    SP_HIP(hipMemcpyAsync(left, d_left, records * 32, hipMemcpyDeviceToHost, st));
-    SP_HIP(hipMemcpyAsync(right, d_right, records * 32, hipMemcpyDeviceToHost, st));
-  }
+  const std::initializer_list<Piece> outs = {{index, records * 8}, {node, records * 32}, {left, records * 32},
+                                             {right, records * 32}};
+  SP_HIP(trip.down(d_idx + n, outs));
   SP_HIP(hipStreamSynchronize(st));
   tl_mark("witness: results on the host");
-  if (stage) {
-    const char* o = stage + in_bytes;
-    std::memcpy(index, o, records * 8);
-    std::memcpy(node, o + records * 8, records * 32);
-    std::memcpy(left, o + records * 40, records * 32);
-    std::memcpy(right, o + records * 72, records * 32);
-  }
+  trip.finish(outs);
   // the level of a record is a function of the level counts alone: filled here, it does not cross PCIe
   size_t u = 0;
   for (unsigned l = 1; l <= height; ++l) {
@@ -1479,16 +1421,14 @@ int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, ui
   if (rc != SP_OK) return rc;
   SparseTree& t = *ts.t;
   const unsigned height = t.height;
-  for (size_t i = 0; i < n; ++i) {
-    if (height < 64 && (keys[i] >> height) != 0) { set_error("key out of range for height"); return SP_ERR_BAD_ARGUMENT; }
-  }
+  if (!keys_ok(height, keys, n, false)) return SP_ERR_BAD_ARGUMENT;
   if (n == 0) return SP_OK;
   if (n > 0x7fffffffull / height) { set_error("too many keys"); return SP_ERR_BAD_ARGUMENT; }
   const size_t pairs = n * height;
   std::vector<uint64_t> emp;
   rc = tree_empty_roots(t, emp);
   if (rc != SP_OK) return rc;
-  if (!t.table) {  // never updated: the empty leaf under a path of empty-subtree roots
+  if (!t.table.ptr) {  // never updated: the empty leaf under a path of empty-subtree roots
     for (size_t i = 0; i < n; ++i) {
       std::memcpy(leaves + 4 * i, emp.data(), 32);
       std::memcpy(siblings + 4 * i * height, emp.data(), (size_t)height * 32);
@@ -1505,18 +1445,9 @@ int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, ui
   uint64_t* d_sib = d_leaves + 4 * n;
   hipStream_t st = t.stream;
   tl_mark("prove: work buffer ready");
-  char* stage = nullptr;
-  if (in_bytes + out_bytes <= PINNED_STAGE_MAX && t.hbuf.reserve(in_bytes + out_bytes) == hipSuccess) stage = (char*)t.hbuf.ptr;
-  else (void)hipGetLastError();
-  if (stage) {
-    std::memcpy(stage, emp.data(), emp_bytes);
-    std::memcpy(stage + emp_bytes, keys, n * 8);
-    SP_HIP(hipMemcpyAsync(d_emp, stage, in_bytes, hipMemcpyHostToDevice, st));
-  } else {
-    SP_HIP(hipMemcpyAsync(d_emp, emp.data(), emp_bytes, hipMemcpyHostToDevice, st));
-    SP_HIP(hipMemcpyAsync(d_keys, keys, n * 8, hipMemcpyHostToDevice, st));
-  }
-  hipLaunchKernelGGL(tree_prove_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, t.table, t.slots - 1,
+  StagedTrip trip(t.hbuf, in_bytes + out_bytes, st);
+  SP_HIP(trip.up(d_emp, {{emp.data(), emp_bytes}, {keys, n * 8}}));
+  hipLaunchKernelGGL(tree_prove_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, t.table.ptr, t.slots - 1,
                      d_keys, height, d_emp, d_leaves, d_sib, (unsigned)pairs);
   SP_HIP(hipGetLastError());
   tl_mark("prove: kernel enqueued");
@@ -1524,18 +1455,11 @@ int sp_tree_prove(int tree, const uint64_t* keys, size_t n, uint64_t* leaves, ui
     SP_HIP(hipStreamSynchronize(st));
     tl_mark("prove: kernel done");
   }
-  if (stage) {
-    SP_HIP(hipMemcpyAsync(stage + in_bytes, d_leaves, out_bytes, hipMemcpyDeviceToHost, st));
-  } else {
-    SP_HIP(hipMemcpyAsync(leaves, d_leaves, n * 32, hipMemcpyDeviceToHost, st));
-    SP_HIP(hipMemcpyAsync(siblings, d_sib, pairs * 32, hipMemcpyDeviceToHost, st));
-  }
+  const std::initializer_list<Piece> outs = {{leaves, n * 32}, {siblings, pairs * 32}};
+  SP_HIP(trip.down(d_leaves, outs));
   SP_HIP(hipStreamSynchronize(st));
   tl_mark("prove: results on the host");
-  if (stage) {
-    std::memcpy(leaves, stage + in_bytes, n * 32);
-    std::memcpy(siblings, stage + in_bytes + n * 32, pairs * 32);
-  }
+  trip.finish(outs);
   return SP_OK;
 }
 
@@ -1573,7 +1497,7 @@ int sp_tree_scan(int tree, uint64_t lo, uint64_t hi, size_t capacity, uint64_t* 
   SparseTree& t = *ts.t;
   const unsigned height = t.height;
   if (height < 64 && (hi >> height) != 0) { set_error("sp_tree_scan: hi out of range for height"); return SP_ERR_BAD_ARGUMENT; }
-  if (!t.table || !t.has_root) {  // never updated: no launch
+  if (!t.table.ptr || !t.has_root) {  // never updated: no launch
     *n = 0;
     *more = 0;
     return SP_OK;
@@ -1597,7 +1521,7 @@ int sp_tree_scan(int tree, uint64_t lo, uint64_t hi, size_t capacity, uint64_t* 
   SP_HIP(t.buf.reserve(z_off + z_bytes + 64));
   char* b = (char*)t.buf.ptr;
   ScanWork w;
-  w.tab = t.table;
+  w.tab = t.table.ptr;
   w.mask = t.slots - 1;
   w.emp = (const uint64_t*)b;
   w.lo = lo;
@@ -1616,16 +1540,10 @@ int sp_tree_scan(int tree, uint64_t lo, uint64_t hi, size_t capacity, uint64_t* 
   tl_mark("scan: work buffer ready");
   // a page up to 4 MiB comes back through the tree's page-locked buffer in one copy; above that the header comes back
   // first and the n keys and leaves go directly into the caller's arrays
-  char* stage = nullptr;
-  const bool whole = emp_bytes + out_bytes <= PINNED_STAGE_MAX;
-  if (t.hbuf.reserve(whole ? emp_bytes + out_bytes : emp_bytes + sizeof(ScanHeader)) == hipSuccess) stage = (char*)t.hbuf.ptr;
-  else (void)hipGetLastError();
-  if (stage) {
-    std::memcpy(stage, emp.data(), emp_bytes);
-    SP_HIP(hipMemcpyAsync(b, stage, emp_bytes, hipMemcpyHostToDevice, st));
-  } else {
-    SP_HIP(hipMemcpyAsync(b, emp.data(), emp_bytes, hipMemcpyHostToDevice, st));
-  }
+  const bool whole = StagedTrip::fits(emp_bytes + out_bytes);
+  StagedTrip trip(t.hbuf, whole ? emp_bytes + out_bytes : emp_bytes + sizeof(ScanHeader), st);
+  char* const stage = trip.stage;
+  SP_HIP(trip.up(b, {{emp.data(), emp_bytes}}));
   SP_HIP(hipMemsetAsync(b + z_off, 0, z_bytes, st));
   hipLaunchKernelGGL(tree_scan_top_kernel, dim3(1), dim3(SCAN_TOP), 0, st, w, height);
   // The frontier of level height - k has at most 2^k nodes, so the top kernel hands over at level height - 11 or
@@ -1646,13 +1564,12 @@ int sp_tree_scan(int tree, uint64_t lo, uint64_t hi, size_t capacity, uint64_t* 
   h.n = 0;
   h.more = 0;
   h.start = 0;
-  if (stage && whole) {
-    SP_HIP(hipMemcpyAsync(stage + emp_bytes, w.hdr, out_bytes, hipMemcpyDeviceToHost, st));
+  if (stage && whole) {  // the whole page in one copy; what the header counts goes on to the caller
+    SP_HIP(trip.down(w.hdr, {{&h, sizeof(h)}, {keys, wide * 8}, {leaves, cap * 32}}));
     SP_HIP(hipStreamSynchronize(st));
-    std::memcpy(&h, stage + emp_bytes, sizeof(h));
+    trip.finish({{&h, sizeof(h)}});
     if (h.n > cap) { set_error("sp_tree_scan: inconsistent count"); return SP_ERR_HIP; }
-    std::memcpy(keys, stage + emp_bytes + sizeof(h), h.n * 8);
-    std::memcpy(leaves, stage + emp_bytes + sizeof(h) + wide * 8, h.n * 32);
+    trip.finish({{nullptr, sizeof(h)}, {keys, h.n * 8}, {nullptr, (wide - h.n) * 8}, {leaves, h.n * 32}});
   } else {
     SP_HIP(hipMemcpyAsync(stage ? (void*)(stage + emp_bytes) : (void*)&h, w.hdr, sizeof(h), hipMemcpyDeviceToHost, st));
     SP_HIP(hipStreamSynchronize(st));
@@ -1693,10 +1610,7 @@ static bool verify_update_args(unsigned height, const uint64_t* keys, size_t n, 
     set_error("sp_merkle_verify_update: null argument");
     return false;
   }
-  for (size_t i = 0; i < n; ++i) {
-    if (i > 0 && keys[i] <= keys[i - 1]) { set_error("keys must be strictly increasing"); return false; }
-    if (height < 64 && (keys[i] >> height) != 0) { set_error("key out of range for height"); return false; }
-  }
+  if (!keys_ok(height, keys, n, true)) return false;
   std::vector<size_t> cnt;
   size_t felts = 0, srcs = 0;
   if (!tree_layout(height, keys, n, cnt, vs.lv, vs.total, felts, vs.idxs, srcs) || 2 * (vs.total - n) >= 0x80000000ull) {
@@ -1722,44 +1636,23 @@ static int enqueue_verify_update(const VerifyShape& vs, const uint64_t* keys, si
   const size_t hash_off = (src_off + R * sizeof(int2) + 31) & ~(size_t)31, hst_off = hash_off + 2 * R * 32;
   const size_t need = hst_off + 2 * R + 64;
   VerifyWork& w = g_verify_work[stream_key(st)];
-  if (need > w.bytes) {
-    if (w.retired) {  // the buffer before the last one: only work older than the last growth can still read it
-      SP_HIP(hipStreamSynchronize(st));
-      (void)hipFree(w.retired);
-      w.retired = nullptr;
-    }
-    void* fresh = nullptr;
-    SP_HIP(hipMalloc(&fresh, need + need / 4));
-    w.retired = w.ptr;
-    w.ptr = fresh;
-    w.bytes = need + need / 4;
-  }
-  char* b = (char*)w.ptr;
+  if (need > w.bytes) SP_HIP(w.grow(need + need / 4, st));
+  char* b = w.ptr;
   uint64_t* d_roots = (uint64_t*)b;
   uint64_t* d_idx = (uint64_t*)(b + idx_off);
   int2* d_src = (int2*)(b + src_off);
   uint64_t* d_hashed = (uint64_t*)(b + hash_off);
   uint8_t* d_hst = (uint8_t*)(b + hst_off);
   // roots and keys are adjacent on the device: one copy out of the page-locked buffer
-  if (w.pending) {
-    SP_HIP(hipEventSynchronize(w.copied));
-    w.pending = false;
-  }
-  if (w.copied == nullptr) SP_HIP(hipEventCreateWithFlags(&w.copied, hipEventDisableTiming));
-  SP_HIP(w.host.reserve(64 + n * 8));
-  std::memcpy(w.host.ptr, prev_root, 32);
-  std::memcpy((char*)w.host.ptr + 32, new_root, 32);
-  std::memcpy((char*)w.host.ptr + 64, keys, n * 8);
-  SP_HIP(hipMemcpyAsync(d_roots, w.host.ptr, 64 + n * 8, hipMemcpyHostToDevice, st));
-  SP_HIP(hipEventRecord(w.copied, st));
-  w.pending = true;
+  int rc = stage_copy({{prev_root, 32}, {new_root, 32}, {keys, n * 8}}, d_roots, st);
+  if (rc != SP_OK) return rc;
   SP_HIP(hipMemsetAsync(verdict, SP_PATH_TRUE, 1, st));
   hipLaunchKernelGGL(tree_level_nodes_kernel, dim3(vs.lv.height), dim3(1024), 0, st, vs.lv, d_idx, d_idx);
   hipLaunchKernelGGL(tree_children_kernel, dim3((unsigned)((vs.total - vs.top + 255) / 256)), dim3(256), 0, st, vs.lv,
                      d_idx, d_src, (unsigned)(vs.total - vs.top));
   SP_HIP(hipGetLastError());
   Scratch s;
-  int rc = get_scratch_public(2 * R, s, st);
+  rc = get_scratch_public(2 * R, s, st);
   if (rc != SP_OK) return rc;
   rc = enqueue_pedersen(left, 1, right, 1, d_hashed, 1, d_hst, nullptr, 2 * R, st, s, nullptr);
   if (rc != SP_OK) return rc;
@@ -1818,23 +1711,9 @@ int sp_merkle_verify_update(unsigned height, const uint64_t* keys, size_t n, con
   uint64_t* d_new = d_prev + 4 * n;
   uint8_t* d_verdict = (uint8_t*)(b + in_bytes);
   uint8_t* d_status = d_verdict + 4;
-  char* stage = nullptr;
-  if (in_bytes + out_bytes <= PINNED_STAGE_MAX && L.hio.reserve(in_bytes + out_bytes) == hipSuccess) stage = (char*)L.hio.ptr;
-  else (void)hipGetLastError();
-  if (stage) {
-    std::memcpy(stage, node, rec_bytes);
-    std::memcpy(stage + rec_bytes, left, rec_bytes);
-    std::memcpy(stage + 2 * rec_bytes, right, rec_bytes);
-    std::memcpy(stage + 3 * rec_bytes, prev_leaves, leaf_bytes);
-    std::memcpy(stage + 3 * rec_bytes + leaf_bytes, new_leaves, leaf_bytes);
-    SP_HIP(hipMemcpyAsync(d_node, stage, in_bytes, hipMemcpyHostToDevice, L.stream));
-  } else {
-    SP_HIP(hipMemcpyAsync(d_node, node, rec_bytes, hipMemcpyHostToDevice, L.stream));
-    SP_HIP(hipMemcpyAsync(d_left, left, rec_bytes, hipMemcpyHostToDevice, L.stream));
-    SP_HIP(hipMemcpyAsync(d_right, right, rec_bytes, hipMemcpyHostToDevice, L.stream));
-    SP_HIP(hipMemcpyAsync(d_prev, prev_leaves, leaf_bytes, hipMemcpyHostToDevice, L.stream));
-    SP_HIP(hipMemcpyAsync(d_new, new_leaves, leaf_bytes, hipMemcpyHostToDevice, L.stream));
-  }
+  StagedTrip trip(L.hio, in_bytes + out_bytes, L.stream);
+  SP_HIP(trip.up(d_node, {{node, rec_bytes}, {left, rec_bytes}, {right, rec_bytes}, {prev_leaves, leaf_bytes},
+                          {new_leaves, leaf_bytes}}));
   int rc;
   {
     ctx_lock lk(ctx().mu);
@@ -1843,17 +1722,11 @@ int sp_merkle_verify_update(unsigned height, const uint64_t* keys, size_t n, con
   }
   if (rc != SP_OK) return rc;
   uint8_t v = SP_PATH_FALSE;  // written by the stream, read after the synchronisation below
-  if (stage) {
-    SP_HIP(hipMemcpyAsync(stage + in_bytes, d_verdict, out_bytes, hipMemcpyDeviceToHost, L.stream));
-  } else {
-    SP_HIP(hipMemcpyAsync(&v, d_verdict, 1, hipMemcpyDeviceToHost, L.stream));
-    if (status) SP_HIP(hipMemcpyAsync(status, d_status, 2 * R, hipMemcpyDeviceToHost, L.stream));
-  }
+  // the verdict byte, the rest of its word, the status bytes when asked for
+  const std::initializer_list<Piece> outs = {{&v, 1}, {nullptr, 3}, {status, out_bytes - 4}};
+  SP_HIP(trip.down(d_verdict, outs));
   SP_HIP(hipStreamSynchronize(L.stream));
-  if (stage) {
-    v = (uint8_t)stage[in_bytes];
-    if (status) std::memcpy(status, stage + in_bytes + 4, 2 * R);
-  }
+  trip.finish(outs);
   *verdict = v;
   return SP_OK;
 }
@@ -2063,7 +1936,7 @@ int sp_state_batch(int positions_tree, int orders_tree, const uint64_t* pos_keys
     set_error("sp_state_batch: the two trees live on different contexts");
     return SP_ERR_BAD_ARGUMENT;
   }
-  if (!tree_keys_ok(P, pos_keys, n_pos) || !tree_keys_ok(O, ord_keys, n_ord)) return SP_ERR_BAD_ARGUMENT;
+  if (!keys_ok(P.height, pos_keys, n_pos, true) || !keys_ok(O.height, ord_keys, n_ord, true)) return SP_ERR_BAD_ARGUMENT;
   tl_mark("trees locked, arguments checked");
 
   // ---- positions: previous chains, then the changed new ones, as one ragged batch ----

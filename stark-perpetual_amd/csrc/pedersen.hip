@@ -1384,10 +1384,11 @@ static int enqueue_pedersen_impl(const uint64_t* x, size_t xs, const uint64_t* y
 // ---- (sp_merkle_fold_paths[_dev], sp_merkle_verify_paths) --------------------------------------------------
 static bool g_chain_ragged = getenv("STARKPERP_NO_CHAIN_RAGGED") == nullptr;  // A/B switch, both forms
 static bool g_path_fold = getenv("STARKPERP_NO_PATH_FOLD") == nullptr;        // A/B switch, the path form only
-// Host-side staging of a ragged call's offsets and keys (in the fallback: of its plan's metadata): page-locked,
-// one per stream, so that the caller's arrays are consumed before the call returns and the copy to the device is a
-// true asynchronous DMA.  The event marks the last copy out of the buffer: it is waited for before the buffer is
-// written again - the only wait of a ragged _dev call, and one for a copy that has long run when the next call comes.
+// Host-side staging of the small host arrays of a _dev call - a ragged call's offsets and keys (in the fallback: its
+// plan's metadata), the roots and keys of sp_merkle_verify_update (merkle.hip): page-locked, one per stream, so that
+// the caller's arrays are consumed before the call returns and the copy to the device is a true asynchronous DMA.
+// The event marks the last copy out of the buffer: it is waited for before the buffer is written again - the only
+// wait of such a call, and one for a copy that has long run when the next call on the stream comes.
 struct RaggedStage {
   PinnedBuffer host;
   hipEvent_t copied = nullptr;
@@ -1401,19 +1402,23 @@ void release_ragged_stage() {
   }
   g_ragged_stage.clear();
 }
-// The host arrays a (a_bytes) and b (b_bytes, may be 0), one behind the other -> d_meta, through the stream's
-// page-locked buffer.
-static int ragged_stage_copy(const void* a, size_t a_bytes, const void* b, size_t b_bytes, void* d_meta, hipStream_t st) {
+// See pedersen.hpp.
+int stage_copy(std::initializer_list<Piece> pieces, void* dev, hipStream_t st) {
   RaggedStage& rs = g_ragged_stage[stream_key(st)];
   if (rs.pending) {
     SP_HIP(hipEventSynchronize(rs.copied));
     rs.pending = false;
   }
   if (rs.copied == nullptr) SP_HIP(hipEventCreateWithFlags(&rs.copied, hipEventDisableTiming));
-  SP_HIP(rs.host.reserve(a_bytes + b_bytes));
-  if (a_bytes) std::memcpy(rs.host.ptr, a, a_bytes);
-  if (b_bytes) std::memcpy((char*)rs.host.ptr + a_bytes, b, b_bytes);
-  SP_HIP(hipMemcpyAsync(d_meta, rs.host.ptr, a_bytes + b_bytes, hipMemcpyHostToDevice, st));
+  size_t bytes = 0;
+  for (const Piece& p : pieces) bytes += p.bytes;
+  SP_HIP(rs.host.reserve(bytes));
+  size_t at = 0;
+  for (const Piece& p : pieces) {
+    if (p.bytes) std::memcpy((char*)rs.host.ptr + at, p.ptr, p.bytes);
+    at += p.bytes;
+  }
+  SP_HIP(hipMemcpyAsync(dev, rs.host.ptr, bytes, hipMemcpyHostToDevice, st));
   SP_HIP(hipEventRecord(rs.copied, st));
   rs.pending = true;
   return SP_OK;
@@ -1450,7 +1455,7 @@ int enqueue_pedersen_fold_ragged(const uint64_t* leaves, const uint64_t* words, 
     SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
     const uint64_t* d_keys = (const uint64_t*)tail;
     const uint32_t* d_off = (const uint32_t*)(tail + key_bytes);
-    rc = ragged_stage_copy(keys, key_bytes, off, off_bytes, tail, st);
+    rc = stage_copy({{keys, key_bytes}, {off, off_bytes}}, tail, st);
     if (rc != SP_OK) return rc;
     for (size_t b = 0; b < n; b += cap) {
       const size_t m = n - b < cap ? n - b : cap;
@@ -1485,7 +1490,7 @@ int enqueue_pedersen_fold_ragged(const uint64_t* leaves, const uint64_t* words, 
   uint32_t* d_meta = (uint32_t*)tail;
   uint8_t* d_stat = (uint8_t*)(tail + meta_bytes);
   uint64_t* d_work = (uint64_t*)(tail + meta_bytes + stat_bytes);
-  rc = ragged_stage_copy(p.meta.data(), p.meta.size() * sizeof(uint32_t), nullptr, 0, d_meta, st);
+  rc = stage_copy({{p.meta.data(), p.meta.size() * sizeof(uint32_t)}}, d_meta, st);
   if (rc != SP_OK) return rc;
   if (sided) SP_HIP(hipMemcpyAsync(d_work + 4 * n, leaves, n * 32, hipMemcpyDeviceToDevice, st));
   if (total > 0) SP_HIP(hipMemcpyAsync(d_work + 4 * (p.work_felts - total), words, total * 32, hipMemcpyDeviceToDevice, st));
@@ -1739,17 +1744,14 @@ int sp_pedersen_chains(const uint64_t* elems, size_t width, size_t depth, uint64
   uint64_t* d_out = d_el + 4 * width * depth;
   // small batches (sp_order_batch's message hashes) in and out through the lane's page-locked buffer: see PinnedBuffer
   const size_t in_bytes = width * depth * 32, out_bytes = width * 32;
-  char* stage = nullptr;
-  if (in_bytes + out_bytes <= PINNED_STAGE_MAX && L.hio.reserve(in_bytes + out_bytes) == hipSuccess) stage = (char*)L.hio.ptr;
-  else (void)hipGetLastError();
-  if (stage) std::memcpy(stage, elems, in_bytes);
-  SP_HIP(hipMemcpyAsync(d_el, stage ? (const void*)stage : (const void*)elems, in_bytes, hipMemcpyHostToDevice, L.stream));
+  StagedTrip trip(L.hio, in_bytes + out_bytes, L.stream);
+  SP_HIP(trip.up(d_el, {{elems, in_bytes}}));
   uint8_t st8 = 0;  // written by the stream (the chains' status flag), read after the synchronisation below
   int rc = sp_pedersen_chains_dev(d_el, width, depth, d_out, &st8, L.stream);
   if (rc != SP_OK) return rc;
-  SP_HIP(hipMemcpyAsync(stage ? (void*)(stage + in_bytes) : (void*)out, d_out, out_bytes, hipMemcpyDeviceToHost, L.stream));
+  SP_HIP(trip.down(d_out, {{out, out_bytes}}));
   SP_HIP(hipStreamSynchronize(L.stream));
-  if (stage) std::memcpy(out, stage + in_bytes, out_bytes);
+  trip.finish({{out, out_bytes}});
   if (status) *status = st8;
   return SP_OK;
 }
@@ -1780,24 +1782,14 @@ int sp_pedersen_chains_ragged(const uint64_t* elems, const uint32_t* off, size_t
   uint64_t* d_el = (uint64_t*)L.io.ptr;
   uint64_t* d_out = d_el + 4 * total;
   uint8_t* d_st = (uint8_t*)(d_out + 4 * n);
-  char* stage = nullptr;
-  if (in_bytes + out_bytes <= PINNED_STAGE_MAX && L.hio.reserve(in_bytes + out_bytes) == hipSuccess) stage = (char*)L.hio.ptr;
-  else (void)hipGetLastError();
-  if (stage) std::memcpy(stage, elems, in_bytes);
-  SP_HIP(hipMemcpyAsync(d_el, stage ? (const void*)stage : (const void*)elems, in_bytes, hipMemcpyHostToDevice, L.stream));
+  StagedTrip trip(L.hio, in_bytes + out_bytes, L.stream);
+  SP_HIP(trip.up(d_el, {{elems, in_bytes}}));
   int rc = sp_pedersen_chains_ragged_dev(d_el, off, n, d_out, d_st, L.stream);
   if (rc != SP_OK) return rc;
-  if (stage) {
-    SP_HIP(hipMemcpyAsync(stage + in_bytes, d_out, out_bytes, hipMemcpyDeviceToHost, L.stream));
-  } else {
-    SP_HIP(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, L.stream));
-    if (status) SP_HIP(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, L.stream));
-  }
+  const std::initializer_list<Piece> outs = {{out, n * 32}, {status, n}};
+  SP_HIP(trip.down(d_out, outs));
   SP_HIP(hipStreamSynchronize(L.stream));
-  if (stage) {
-    std::memcpy(out, stage + in_bytes, n * 32);
-    if (status) std::memcpy(status, stage + in_bytes + n * 32, n);
-  }
+  trip.finish(outs);
   return SP_OK;
 }
 

@@ -1,5 +1,5 @@
-// What pedersen.hip offers the other translation units of the library (merkle.hip): the per-stream scratch, the level
-// and walk launchers.  One definition of every struct that crosses the boundary - PathLevels is passed BY VALUE into a
+// What pedersen.hip offers the other translation units of the library (merkle.hip): the per-stream scratch and
+// page-locked staging copy, the level and walk launchers.  One definition of every struct that crosses the boundary - PathLevels is passed BY VALUE into a
 // kernel, so two hand-kept copies of it would be an ODR hazard nothing checks.
 #pragma once
 #include "context.hpp"
@@ -12,6 +12,11 @@ struct Scratch {
 };
 // The stream's scratch planes for n hashes (grown on demand) and its status flag.
 int get_scratch_public(size_t n, Scratch& s, hipStream_t st);
+
+// The host `pieces`, one behind the other -> dev: memcpy into the stream's page-locked buffer, then one asynchronous
+// copy.  The buffer is guarded by an event that marks the last copy out of it, so the pieces are consumed when this
+// returns; calls on one stream share buffer and event.  The caller holds the context lock.
+int stage_copy(std::initializer_list<Piece> pieces, void* dev, hipStream_t st);
 
 // Enqueue n hashes; x/y/out strides in felts.  `flag` (device, may be null) ORs item status.
 int enqueue_pedersen(const uint64_t* x, size_t xs, const uint64_t* y, size_t ys, uint64_t* out,

@@ -83,6 +83,28 @@ def test_chains_and_paths_fold_the_same_data(batch_np):
     assert batch_np.ints_from_felts(got_c) == cases.oracle_fold(chains)
 
 
+def test_a_batch_above_the_staging_limit_equals_the_equal_length_call(batch_np):
+    """sp_pedersen_chains_ragged sends off[n] x 32 + 33 n bytes through page-locked memory up to 4 MiB and copies
+    directly above (csrc/context.hpp StagedTrip); the largest batch above is 8200 chains, under 1 MiB.  33 000 chains of
+    4 words are 5 313 000 bytes: hashes and status bytes come back in two direct copies.  The same chains through
+    sp_pedersen_chains (word-major, pinned at this size by tests/test_gpu_pedersen.py) give the same rows."""
+    n, depth = 33000, 4
+    assert n * depth * 32 + 33 * n > 4 << 20
+    rng = np.random.default_rng(33)
+    words = rng.integers(0, 2**63, size=(depth, n, 4), dtype=np.uint64)
+    words[:, :, 3] >>= np.uint64(8)  # below p
+    chain_major = np.ascontiguousarray(words.transpose(1, 0, 2)).reshape(n * depth, 4)
+    got, status = batch_np.pedersen_chains_ragged(chain_major, np.arange(n + 1, dtype=np.uint32) * np.uint32(depth))
+    assert not status.any()
+    assert (got == batch_np.pedersen_chains(words)).all()
+    # the status bytes travel too: word 2 of chain 12345 becomes p, and that chain alone is flagged
+    chain_major[12345 * depth + 2] = batch_np.felts_from_ints([R.FIELD_PRIME])[0]
+    again, status = batch_np.pedersen_chains_ragged(chain_major, np.arange(n + 1, dtype=np.uint32) * np.uint32(depth))
+    assert np.flatnonzero(status).tolist() == [12345] and status[12345] & 1  # SP_HASH_OUT_OF_RANGE
+    keep = np.arange(n) != 12345
+    assert (again[keep] == got[keep]).all()
+
+
 class CountingLib:
     """The binding with the calls of the chain entry points counted."""
 

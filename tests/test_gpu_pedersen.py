@@ -202,6 +202,23 @@ def test_bulk_and_split_paths_vs_c_oracle(batch):
         assert batch.pedersen_hash_many(xs, ys) == exp, n
 
 
+def test_chains_above_the_staging_limit_equal_their_two_halves():
+    """sp_pedersen_chains sends width x depth + width felts through page-locked memory up to 4 MiB and copies directly
+    above (csrc/context.hpp StagedTrip).  33 000 chains of 4 words are 5 280 000 bytes: direct.  Either half is
+    2 640 000: staged.  The kernels see the same chains both ways, so the results are equal row by row."""
+    import numpy as np
+    from starkperp import batch_np
+    width, depth, half = 33000, 4, 16500
+    assert (width * depth + width) * 32 > 4 << 20 >= (half * depth + half) * 32
+    rng = np.random.default_rng(4)
+    words = rng.integers(0, 2**63, size=(depth, width, 4), dtype=np.uint64)
+    words[:, :, 3] >>= np.uint64(8)  # below p
+    whole = batch_np.pedersen_chains(words)
+    assert (whole[:half] == batch_np.pedersen_chains(words[:, :half])).all()
+    assert (whole[half:] == batch_np.pedersen_chains(words[:, half:])).all()
+    assert len({row.tobytes() for row in whole}) == width  # no row was left as it came, or copied from another
+
+
 def test_forest_roots_equal_individual_roots(batch):
     trees = [wl.leaves(256, seed=300 + i) for i in range(7)]
     assert batch.merkle_roots_many(trees) == [batch.merkle_root(t) for t in trees]

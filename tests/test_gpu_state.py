@@ -251,6 +251,34 @@ def test_library_tree_large_batches_and_table_growth():
     lib_tree.close()
 
 
+def test_library_tree_update_above_the_staging_limit_equals_two_staged_updates():
+    """An update's inputs - (h + 1) 32 + 32 n + 8 n + 64 bytes - go through the tree's page-locked buffer up to 4 MiB and
+    in direct copies above (csrc/merkle.hip tree_enqueue); the batches above stop at 5000 keys.  105 000 of the 131 072
+    keys of a height-17 tree are 4 200 640 bytes: direct.  A second tree takes the same leaves in two updates of 52 500
+    (2 100 640 bytes each: staged) and must end at the same root and hold the same leaves."""
+    import numpy as np
+    from starkperp import batch_np, state
+    n, height = 105000, 17
+    size = lambda m: (height + 1) * 32 + 40 * m + 64
+    assert size(n // 2) <= 4 << 20 < size(n)
+    rng = np.random.default_rng(17)
+    keys = np.sort(rng.choice(1 << height, size=n, replace=False).astype(np.uint64))
+    leaves = rng.integers(1, 2**63, size=(n, 4), dtype=np.uint64)
+    leaves[:, 3] >>= np.uint64(8)  # below p
+    one, two = state.LibrarySparseTree(height, 0), state.LibrarySparseTree(height, 0)
+    empty_root, root = one.update_arrays(keys, leaves)
+    assert empty_root == two.root and root != empty_root
+    half = n // 2
+    first = two.update_arrays(keys[:half], leaves[:half])
+    second = two.update_arrays(keys[half:], leaves[half:])
+    assert first[0] == empty_root and second[0] == first[1] and second[1] == root == one.root == two.root
+    probe = [0, 1, half - 1, half, n - 2, n - 1] + [int(i) for i in rng.choice(n, size=26, replace=False)]
+    expected = batch_np.ints_from_felts(leaves[probe])
+    for tree in (one, two):
+        assert tree.get_many([int(k) for k in keys[probe]]) == expected
+    one.close(), two.close()
+
+
 def test_library_tree_grows_through_three_tables_without_losing_a_node():
     """Round 6 growth policy (csrc/merkle.hip tree_reserve): a table that must grow is sized for four times the need,
     the rehash is enqueued on the tree's stream and the OLD table is retired, not freed, until the next growth.  48

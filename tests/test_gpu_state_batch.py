@@ -384,6 +384,33 @@ def test_state_batch_slices_above_the_ragged_launch_class():
     one.close(), two.close()
 
 
+def test_state_batch_above_the_staging_limit_matches_the_separate_calls():
+    """The positions tree's share of a batch - its update's inputs and the position words behind them - goes through the
+    tree's page-locked buffer up to 4 MiB and in direct copies above (csrc/merkle.hip tree_enqueue, sp_state_batch); the
+    batch above carries about 0.8 MiB.  2050 positions of 62 assets are 2050 x (3 + 65) words = 4 460 800 bytes of words
+    alone: direct.  The 64 orders still stage.  Compared, as above, with the separate-call route on a second pair."""
+    from starkperp import batch_np, state
+    rng = random.Random(62)
+    one, two = state.SharedState(20, 20), state.SharedState(20, 20)
+    keys = sorted(rng.sample(range(2**20), 2050))
+    pos = [(k, EMPTY, random_position(rng, 62)) for k in keys]
+    orders = [(k, 0, rng.randrange(P)) for k in sorted(rng.sample(range(2**20), 64))]
+    arrays = state.pack_state_batch(pos, orders)
+    assert (arrays[1].shape[0] + arrays[3].shape[0]) * 32 > 4 << 20
+    p_roots, o_roots, p_st, o_st, b_st = batch_np.state_batch(one.positions, one.orders, *arrays)
+    assert b_st == 0 and not p_st.any() and not o_st.any()
+    assert (p_roots, o_roots) == two._apply_in_separate_calls(pos, orders)
+    assert (one.positions_root, one.orders_root) == (two.positions_root, two.orders_root) == (p_roots[1], o_roots[1])
+    probe = rng.sample(keys, 40) + [keys[0], keys[-1], rng.randrange(2**20)]
+    assert one.positions.get_many(probe) == two.positions.get_many(probe)
+    # a stale previous position in a batch of this size: the status bytes come back directly too
+    stale = [(k, q if i != 1000 else EMPTY, random_position(rng, 62)) for i, (k, _, q) in enumerate(pos)]
+    got = batch_np.state_batch(one.positions, one.orders, *state.pack_state_batch(stale, []))
+    assert got[4] == NOT_COMMITTED | PREV_MISMATCH and np.flatnonzero(got[2]).tolist() == [1000]
+    assert got[2][1000] == PREV_MISMATCH and one.positions_root == p_roots[1]
+    one.close(), two.close()
+
+
 def test_shared_state_goes_through_the_one_call_and_raises_the_same_texts(monkeypatch):
     """SharedState with library trees: equal to the oracle twin over two batches (through sp_state_batch: the
     separate-call route is made unreachable), and the assertion texts of the separate-call route for a stale

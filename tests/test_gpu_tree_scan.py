@@ -125,6 +125,27 @@ def test_many_blocks():
     tree.close()
 
 
+def test_a_page_above_the_staging_limit_equals_a_staged_one():
+    """The page's capacity decides how it travels, not what the tree holds: (h + 1) 32 + 16 + (cap + 2) 8 + cap 32 bytes
+    come back through the tree's page-locked buffer in one copy up to 4 MiB; above, the header comes back first and the
+    n keys and leaves follow directly (csrc/merkle.hip sp_tree_scan).  Capacity 4096 is 0.16 MiB, capacity 2^17 is
+    5 MiB: the same 100 keys both ways."""
+    from starkperp import batch_np
+    size = lambda cap: 65 * 32 + 16 + (cap + 2) * 8 + cap * 32
+    assert size(4096) <= 4 << 20 < size(1 << 17)
+    rng = random.Random(17)
+    mods = C.leaves_for(rng, C.distinct_keys(rng, 64, 100, (0, TOP64)))
+    tree = lib_tree(64)
+    write(tree, mods)
+    small, large = (batch_np.tree_scan(tree, 0, TOP64, cap) for cap in (4096, 1 << 17))
+    assert large[0].tolist() == sorted(mods) and not large[2]
+    assert (small[0] == large[0]).all() and (small[1] == large[1]).all() and small[2] == large[2]
+    lo, hi = sorted(mods)[10] + 1, sorted(mods)[60]
+    small, large = (batch_np.tree_scan(tree, lo, hi, cap) for cap in (4096, 1 << 17))
+    assert len(large[0]) == 50 and (small[0] == large[0]).all() and (small[1] == large[1]).all()
+    tree.close()
+
+
 # ---- 4. the cut ------------------------------------------------------------------------------------------------------
 def test_the_cut_above_level_0():
     """700 leaves, 600 of them under one level-12 node: the frontiers above level 12 have about 100 nodes, the ones below

@@ -117,6 +117,31 @@ def test_witness_after_the_slot_table_has_grown():
     lib_tree.close()
 
 
+def test_proofs_on_both_sides_of_the_staging_limit_equal_their_two_halves():
+    """sp_tree_prove moves (h + 1) 32 + 8 n + (n + n h) 32 bytes: through the tree's page-locked buffer up to 4 MiB, in
+    direct copies above (csrc/context.hpp StagedTrip).  At height 64 that is 2080 + 2088 n: 2007 keys are the most that
+    stage, 2008 are the fewest that do not (the sets above stop at 303).  Both calls must agree, key by key, with the
+    proofs of the same keys asked for in two halves (staged, compared with the twin above)."""
+    from starkperp import batch_np, state
+    size = lambda n: 65 * 32 + 8 * n + (n + 64 * n) * 32
+    assert size(2007) <= 4 << 20 < size(2008)
+    rng = random.Random(2008)
+    tree = state.LibrarySparseTree(64, 0)
+    written = distinct_keys(rng, 64, 600)
+    tree.update_arrays(np.array(written, dtype=np.uint64),
+                       batch_np.felts_from_ints([rng.randrange(1, P) for _ in written]))
+    keys = written + [k ^ 1 for k in written[:300]] + distinct_keys(rng, 64, 1108)
+    rng.shuffle(keys)
+    keys = np.array(keys[:2008], dtype=np.uint64)
+    halves = [batch_np.tree_prove(tree, part) for part in (keys[:1004], keys[1004:])]
+    leaves, siblings = (np.concatenate([h[i] for h in halves]) for i in (0, 1))
+    assert len({row.tobytes() for row in leaves}) > 600  # written leaves are distinct, the others are the empty leaf
+    for n in (2007, 2008):
+        got_leaves, got_siblings = batch_np.tree_prove(tree, keys[:n])
+        assert (got_leaves == leaves[:n]).all() and (got_siblings == siblings[:n]).all(), n
+    tree.close()
+
+
 # ---- the sp_state_batch route ------------------------------------------------------------------------
 def oracle_position_hashes(positions):
     return [R.position_hash(p[0], p[1], list(p[2]), hash_function=oracle_hash) for p in positions]

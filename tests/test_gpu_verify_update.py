@@ -139,6 +139,32 @@ def test_a_consistent_forgery_fails_on_the_sibling_check_alone(name):
     assert state.verify_multi_update(honest, inst.height, inst.prev_root, inst.new_root, mods) is True
 
 
+def test_witnesses_above_the_staging_limit_go_up_in_direct_copies():
+    """The host call moves 3 (2 R 32) + 2 n 32 + 4 + 2 R bytes: through the lane's page-locked buffer up to 4 MiB, in
+    direct copies above (csrc/context.hpp StagedTrip).  Case D (R about 1.7 x 10^4) stays below; 400 random keys at
+    height 64 have R >= 21 850 and cross.  Witnesses straight from sp_tree_witness before and after one update: the
+    verdict is true and every status byte 0; one felt of one record flipped: false, and that record is flagged."""
+    from starkperp import batch_np, state
+    rng = random.Random(400)
+    tree = state.LibrarySparseTree(64, 0)
+    tree.update({rng.randrange(2**64): rng.randrange(1, W.P) for _ in range(300)})
+    keys = np.array(sorted({rng.randrange(2**64) for _ in range(400)}), dtype=np.uint64)
+    n, records = len(keys), batch_np.tree_witness_size(64, keys)
+    assert 3 * (2 * records * 32) + 2 * n * 32 + 4 + 2 * records > 4 << 20
+    prev = batch_np.felts_from_ints(tree.get_many(keys.tolist()))
+    new = batch_np.felts_from_ints([rng.randrange(1, W.P) for _ in range(n)])
+    before = batch_np.tree_witness(tree, keys)
+    prev_root, new_root = tree.update_arrays(keys, new)
+    after = batch_np.tree_witness(tree, keys)
+    tree.close()
+    verdict, status = batch_np.merkle_verify_update(64, keys, prev, new, prev_root, new_root, before, after)
+    assert verdict is True and status.shape == (2, records) and not status.any()
+    u = records // 3
+    after[2][u, 0] ^= np.uint64(1)  # the node value of one record of the after half
+    verdict, status = batch_np.merkle_verify_update(64, keys, prev, new, prev_root, new_root, before, after)
+    assert verdict is False and status[1, u] != 0 and not status[0].any()
+
+
 def test_bad_arguments_write_nothing_and_no_keys_compare_the_roots():
     import torch
     from starkperp import _lib

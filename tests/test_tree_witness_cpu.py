@@ -71,6 +71,37 @@ def test_witness_size_rejects_bad_keys_and_heights():
         assert size_call(height, keys) == (BAD_ARGUMENT, 12345), name
 
 
+ORDER_TEXT = "keys must be strictly increasing"
+RANGE_TEXT = "key out of range for height"
+
+
+def test_key_check_edges_and_error_texts():
+    """The library's one key check (order and range), reached through the caller that needs no device.  Every expectation
+    is the definition: keys strictly increasing, every key below 2^height; a height-64 tree takes every 64-bit key."""
+    from starkperp import _lib
+    top64 = (1 << 64) - 1
+    for name, (height, keys, text) in {
+        "height 1, one key": (1, [1], None),
+        "height 1, both keys": (1, [0, 1], None),
+        "height 64, one key": (64, [top64], None),
+        "height 64, the last two keys": (64, [top64 - 1, top64], None),
+        "height 63, the last key": (63, [(1 << 63) - 1], None),
+        "equal neighbours": (64, [5, 5], ORDER_TEXT),
+        "equal neighbours, height 1": (1, [1, 1], ORDER_TEXT),
+        "decreasing neighbours": (64, [0, top64, top64 - 1], ORDER_TEXT),
+        "decreasing neighbours, height 1": (1, [1, 0], ORDER_TEXT),
+        "2^h alone, height 1": (1, [2], RANGE_TEXT),
+        "2^h behind valid keys, height 1": (1, [0, 1, 2], RANGE_TEXT),
+        "2^h alone, height 63": (63, [1 << 63], RANGE_TEXT),
+        "2^h behind a valid key, height 63": (63, [(1 << 63) - 1, 1 << 63], RANGE_TEXT),
+    }.items():
+        if text is None:
+            assert size_call(height, keys) == (0, witness_size(height, keys)), name
+        else:
+            assert size_call(height, keys) == (BAD_ARGUMENT, 12345), name
+            assert _lib.last_error() == text, name
+
+
 def test_witness_size_runs_before_sp_init():
     """A process that never initialises the library (and could not: no device is asked for) gets the count."""
     code = ("import ctypes, sys\n"
