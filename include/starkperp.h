@@ -255,6 +255,55 @@ int sp_tree_scan(int tree, uint64_t lo, uint64_t hi, size_t capacity,
 /* The tree's node table as it stands: *entries = slots in use (nodes ever written, at any level: it never shrinks, a
  * leaf set back to the empty leaf keeps its path), *slots = the table's slot count (48 bytes each).  Read-only. */
 int sp_tree_table_size(int tree, uint64_t* entries, uint64_t* slots);
+/* A second handle holding the same tree: a checkpoint to roll back to, a fork to try a batch on, a base to diff against.
+ * *clone receives a new handle on the context of `tree` with the same height, empty leaf and root; the node table (same
+ * slot count) and its entry counter are copied device to device, nothing is hashed.  The clone has its own stream, work
+ * buffer, staging buffer and mutex, made by its first call as a created tree's are.  The call holds the source's mutex
+ * from start to end; the copies run on the source's stream, behind its last commit, and are finished when the call
+ * returns.  Afterwards the two handles are independent: updating or destroying either leaves the other untouched.  A
+ * tree that has never been updated has no table: its clone is a fresh tree of the same height and empty leaf, made
+ * without device work.  The table is copied as it stands (a compacting copy is snapshot + restore).
+ * SP_ERR_BAD_ARGUMENT, with nothing written: an unknown or destroyed handle, a null `clone`.  An allocation or copy
+ * that fails returns SP_ERR_HIP: no handle is created and the source stays as it was.
+ * Cost: the device-to-device copy of the table, 48 bytes per slot.  Measured (tools/quick_tree_diff.py,
+ * profiles/tree_diff.txt): 1.67 ms for a height-64 tree of 2^18 keys (a 3.2 GB table), allocation
+ * included, beside 32 ms for restoring its snapshot. */
+int sp_tree_clone(int tree, int* clone);
+/* Ordered diff: WHERE two trees differ.  Writes the first min(capacity, SP_TREE_DIFF_MAX, count) keys k with
+ * lo <= k <= hi (both bounds inclusive, so 2^64 - 1 is reachable), ascending, whose leaf in tree_a differs from the
+ * leaf in tree_b; leaves_a receives the leaf of A at each key and leaves_b the leaf of B (*n felts each), *n the number
+ * written.  A key that a tree has never written, or has set back to the empty leaf, reads as the empty leaf.  *more = 1
+ * if and only if at least one further differing key exists in the range: resume with lo = keys[*n - 1] + 1.  Host
+ * pointers, synchronous.
+ * The comparison is by VALUE: a position absent from a table reads as the empty-subtree root of its level, so a path
+ * that A holds with empty-root values (a leaf written and set back) equals B's missing entry and is not reported.
+ * The device walks down from the two roots, one step per level: the frontier of level l is the ascending list of nodes
+ * whose key interval meets [lo, hi] and whose value in A differs from its value in B; the frontier of level 0 is the
+ * answer.  (1) Both tables are consistent hash trees: equal leaves below a node give equal nodes, so a kept node has a
+ * differing leaf below it, and equal nodes mean equal subtrees (up to a hash collision), so a pruned node has none.
+ * (2) Hence a frontier may be cut at any level - above level 0 to its first capacity + 2 nodes, since only the first
+ * and the last node of a frontier can stick out of [lo, hi] and hold no differing leaf IN RANGE - and a cut at any level
+ * means `more`.  (3) No node interval is computed with a shift by 64: the root's interval is never tested.
+ * SP_ERR_BAD_ARGUMENT, with nothing written: an unknown or destroyed handle, the same handle twice, trees of different
+ * heights, of different empty leaves or on different contexts of sp_init_devices, lo > hi, hi >= 2^height when
+ * height < 64, capacity == 0, a null pointer.  Equal roots - two trees never updated among them - answer *n = 0,
+ * *more = 0 without a launch; ONE tree without a table is walked as a table in which every probe finds nothing.
+ * Locking: both trees' mutexes from start to end, taken in ascending handle order whichever argument a tree is (as
+ * sp_state_batch takes them: sp_tree_diff(a, b) beside sp_tree_diff(b, a) cannot block), so a page describes a batch
+ * boundary of BOTH trees.  The work runs on the stream and in the work buffer of the lower handle, after a wait for the
+ * other tree's stream.
+ * Cost: proportional to height x *n, four table probes per node kept (two children in two tables, loaded together);
+ * never to the size of either table.  Launches as sp_tree_scan's: one for the narrow top, which finishes a page of up to
+ * 1022 keys alone, then one per level.  One copy back (count, more, keys, both runs of leaves) through the page-locked
+ * buffer for a page up to 4 MiB, above that the count first and then exactly *n keys and two runs of *n leaves.
+ * Measured (tools/quick_tree_diff.py, profiles/tree_diff.txt; height 64): a page of 4096 keys on two
+ * trees that differ in all their 4096 keys 1.09 ms (device part 1.04 ms) beside 0.78 ms for sp_tree_scan of such a
+ * page; 1.15 ms on two trees of 2^18 keys that differ in 4096, beside 9.6 ms for a snapshot of both and a compare on
+ * the host; a page of 256 keys 0.59 ms. */
+/* capacity above SP_TREE_DIFF_MAX is treated as SP_TREE_DIFF_MAX: page with `more` */
+#define SP_TREE_DIFF_MAX SP_TREE_SCAN_MAX
+int sp_tree_diff(int tree_a, int tree_b, uint64_t lo, uint64_t hi, size_t capacity,
+                 uint64_t* keys, uint64_t* leaves_a, uint64_t* leaves_b, size_t* n, int* more);
 /* Verifying inclusion proofs: Merkle paths folded on the device, all of a call in ONE launch (ped_fold_ragged_kernel)
  * that lasts as long as its longest path.  node = pedersen_hash(left, right) (signature.py:296-318); bit l of keys[i]
  * says whether the running node is the RIGHT child at level l (starkware/python/merkle_tree.py:4-26,
@@ -331,7 +380,7 @@ int sp_merkle_verify_update(unsigned height, const uint64_t* keys, size_t n, con
                             const uint64_t* node, const uint64_t* left, const uint64_t* right, size_t n_records,
                             uint8_t* verdict, uint8_t* status);
 /* Threading of the sp_tree_* calls (sp_tree_update, sp_tree_get, sp_tree_root, sp_tree_witness, sp_tree_prove,
- * sp_tree_scan, sp_tree_table_size, sp_tree_destroy): a tree has its own HIP stream, work buffer and mutex.  An operation holds
+ * sp_tree_scan, sp_tree_clone, sp_tree_diff, sp_tree_table_size, sp_tree_destroy): a tree has its own HIP stream, work buffer and mutex.  An operation holds
  * the tree's mutex from start to end and the library lock only while it enqueues; the device work of an update
  * (the level launches) runs without the library lock, so other trees and the stateless batches go on meanwhile. */
 /* BASELINE.json configs[2] in one call (services/perpetual/cairo/order/limit_order.cairo:24-52, order.cairo:23-31,

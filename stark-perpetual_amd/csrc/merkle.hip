@@ -824,6 +824,267 @@ tree_scan_step_kernel(ScanWork w, unsigned level) {
   }
 }
 
+// ---- ordered list of the keys whose leaves differ between two trees (sp_tree_diff): the scan's descent from TWO roots ----
+// The frontier of level l is the ascending list of node indices at level l whose key interval meets [lo, hi] and whose
+// value in table A differs from its value in table B; a position absent from a table reads as the empty-subtree root of
+// its level (both trees have one empty leaf, so one array of empty roots serves both).  The three properties of the
+// scan carry over:
+//   1. PRUNING COMPARES VALUES (diff_mark): both tables are consistent hash trees, so equal leaves below a node give
+//      equal nodes - a kept node has a differing leaf below it - and equal nodes mean equal subtrees, up to a hash
+//      collision - a pruned node has none.  A path that A holds with empty-root values (a leaf written and set back)
+//      equals B's missing entry and is pruned.
+//   2. THE CUT (diff_limit): the differing leaf below a kept node is in range unless the node's interval sticks out of
+//      [lo, hi], which only the first and the last node of a frontier can do; frontiers above level 0 keep cap + 2
+//      nodes, level 0 keeps cap, a cut at any level means `more` - the scan's argument word for word.
+//   3. SHIFTS: only children are probed (levels <= 63), scan_meets guards level < 64, the root is never tested.
+// The scan kernels above stay as they are: the diff has kernels of its own with the scan's launch shape, work-buffer
+// layout (one more run of leaves) and position arithmetic, and shares the __device__ helpers (scan_meets, scan_load,
+// scan_wave_sum, tree_mix, ScanHeader, SCAN_TOP, SCAN_BLOCK).  What differs is the probe: FOUR home slots per emitted
+// node - two children in two tables whose masks differ - twelve 16-byte loads issued before the first use, and linear
+// probing that continues in each table on its own.  A tree that was never updated has no table: its probes go to
+// `none`, one zeroed slot of the work buffer (mask 0), so "absent" is what every probe of it answers and no load of
+// the other table waits behind a branch.
+struct DiffWork {
+  const TreeSlot* tab[2];    // A, B; nullptr: no table, every probe answers the level's empty root
+  uint64_t mask[2];          // 0 beside a null table
+  const TreeSlot* none;      // one slot of zeros
+  const uint64_t* emp;       // empty-subtree roots of levels 0 .. height
+  uint64_t lo, hi;
+  unsigned cap, blocks;      // blocks = ceil((cap + 2) / SCAN_BLOCK): entries of tot per level
+  ScanHeader* hdr;
+  uint64_t* frontier[2];
+  uint8_t* marks[2];
+  unsigned* cnt;
+  unsigned* tot;
+  uint64_t* leaves[2];       // of A, of B
+};
+// property 2: how many nodes the frontier of `level` keeps
+__device__ __forceinline__ unsigned diff_limit(const DiffWork& w, unsigned level) { return level ? w.cap + 2 : w.cap; }
+struct DiffValue {
+  uint4 v[2];
+};
+__device__ __forceinline__ const TreeSlot* diff_table(const DiffWork& w, unsigned t) { return w.tab[t] ? w.tab[t] : w.none; }
+// value of (level, index) in table t; `s` is the slot at the key's home `i`; absent: the level's empty root (e0, e1)
+__device__ __forceinline__ DiffValue diff_value(const TreeSlot* tab, uint64_t mask, unsigned level, uint64_t index,
+                                                uint64_t i, ScanSlot s, uint4 e0, uint4 e1) {
+  DiffValue out;
+  for (;;) {
+    if (s.head.w == 0) {
+      out.v[0] = e0;
+      out.v[1] = e1;
+      return out;
+    }
+    if (s.head.w == 2 && s.head.z == level + 1 && s.head.x == (uint32_t)index && s.head.y == (uint32_t)(index >> 32)) {
+      out.v[0] = s.v[0];
+      out.v[1] = s.v[1];
+      return out;
+    }
+    i = (i + 1) & mask;
+    s = scan_load(tab, i);
+  }
+}
+__device__ __forceinline__ bool diff_differs(const DiffValue& a, const DiffValue& b) {
+  const uint32_t d = (a.v[0].x ^ b.v[0].x) | (a.v[0].y ^ b.v[0].y) | (a.v[0].z ^ b.v[0].z) | (a.v[0].w ^ b.v[0].w) |
+                     (a.v[1].x ^ b.v[1].x) | (a.v[1].y ^ b.v[1].y) | (a.v[1].z ^ b.v[1].z) | (a.v[1].w ^ b.v[1].w);
+  return d != 0;
+}
+// Every word of the slots just loaded is an input of ONE empty statement: all their loads are issued before the first
+// use, one trip to memory for the whole probe.  Without it the compiler sinks the loads of one child behind the branch
+// on scan_meets and folds the home-slot load of another into its probing loop (seen in the device assembly: nine of
+// the twelve loads of diff_mark in flight at the first wait, in two groups).
+typedef uint32_t diff_w4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ diff_w4 diff_words(uint4 u) { return diff_w4{u.x, u.y, u.z, u.w}; }
+__device__ __forceinline__ void diff_hold(const ScanSlot& a, const ScanSlot& b) {
+  asm volatile("" ::"v"(diff_words(a.head)), "v"(diff_words(a.v[0])), "v"(diff_words(a.v[1])), "v"(diff_words(b.head)),
+               "v"(diff_words(b.v[0])), "v"(diff_words(b.v[1])));
+}
+__device__ __forceinline__ void diff_hold(const ScanSlot& a, const ScanSlot& b, const ScanSlot& c, const ScanSlot& d) {
+  asm volatile("" ::"v"(diff_words(a.head)), "v"(diff_words(a.v[0])), "v"(diff_words(a.v[1])), "v"(diff_words(b.head)),
+               "v"(diff_words(b.v[0])), "v"(diff_words(b.v[1])), "v"(diff_words(c.head)), "v"(diff_words(c.v[0])),
+               "v"(diff_words(c.v[1])), "v"(diff_words(d.head)), "v"(diff_words(d.v[0])), "v"(diff_words(d.v[1])));
+}
+// which children of node (level, index), level >= 1, are kept (property 1): the four home slots - left and right child
+// in A and in B - and the empty root are loaded at once, then each table is probed on along its own chain
+__device__ __forceinline__ unsigned diff_mark(const DiffWork& w, unsigned level, uint64_t index) {
+  const unsigned below = level - 1;
+  const TreeSlot* ta = diff_table(w, 0);
+  const TreeSlot* tb = diff_table(w, 1);
+  const uint64_t hl = tree_mix(2 * index, below), hr = tree_mix(2 * index + 1, below);
+  const uint64_t al = hl & w.mask[0], ar = hr & w.mask[0], bl = hl & w.mask[1], br = hr & w.mask[1];
+  const ScanSlot sal = scan_load(ta, al), sar = scan_load(ta, ar), sbl = scan_load(tb, bl), sbr = scan_load(tb, br);
+  const uint4* e = reinterpret_cast<const uint4*>(w.emp + 4 * below);
+  const uint4 e0 = e[0], e1 = e[1];
+  diff_hold(sal, sar, sbl, sbr);
+  unsigned mark = 0;
+  if (scan_meets(2 * index, below, w.lo, w.hi) &&
+      diff_differs(diff_value(ta, w.mask[0], below, 2 * index, al, sal, e0, e1),
+                   diff_value(tb, w.mask[1], below, 2 * index, bl, sbl, e0, e1)))
+    mark |= 1u;
+  if (scan_meets(2 * index + 1, below, w.lo, w.hi) &&
+      diff_differs(diff_value(ta, w.mask[0], below, 2 * index + 1, ar, sar, e0, e1),
+                   diff_value(tb, w.mask[1], below, 2 * index + 1, br, sbr, e0, e1)))
+    mark |= 2u;
+  return mark;
+}
+// key and both leaves of position p of the answer
+__device__ __forceinline__ void diff_leaf(const DiffWork& w, uint64_t key, unsigned p) {
+  const TreeSlot* ta = diff_table(w, 0);
+  const TreeSlot* tb = diff_table(w, 1);
+  const uint64_t h = tree_mix(key, 0);
+  const uint64_t ia = h & w.mask[0], ib = h & w.mask[1];
+  const ScanSlot sa = scan_load(ta, ia), sb = scan_load(tb, ib);
+  const uint4* e = reinterpret_cast<const uint4*>(w.emp);
+  const uint4 e0 = e[0], e1 = e[1];
+  diff_hold(sa, sb);
+  const DiffValue v[2] = {diff_value(ta, w.mask[0], 0, key, ia, sa, e0, e1), diff_value(tb, w.mask[1], 0, key, ib, sb, e0, e1)};
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    uint64_t* out = w.leaves[t] + 4 * (size_t)p;  // 8-byte aligned only: cap + 2 keys lie in front
+    out[0] = v[t].v[0].x | (uint64_t)v[t].v[0].y << 32;
+    out[1] = v[t].v[0].z | (uint64_t)v[t].v[0].w << 32;
+    out[2] = v[t].v[1].x | (uint64_t)v[t].v[1].y << 32;
+    out[3] = v[t].v[1].z | (uint64_t)v[t].v[1].w << 32;
+  }
+}
+// The narrow top in one workgroup, frontiers in LDS: tree_scan_top_kernel with diff_mark / diff_leaf.
+__global__ void __launch_bounds__(SCAN_TOP)
+tree_diff_top_kernel(DiffWork w, unsigned height) {
+  __shared__ unsigned wave_tot[SCAN_TOP / 64];
+  __shared__ uint64_t fr[2][2 * SCAN_TOP];
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned level = height, cnt = 1, more = 0;
+  if (threadIdx.x == 0) fr[height & 1][0] = 0;  // the root; the host has compared the two roots (property 3)
+  __syncthreads();
+  while (level > 0 && cnt <= SCAN_TOP) {
+    const uint64_t* cur = fr[level & 1];
+    uint64_t* next = fr[(level - 1) & 1];  // total <= 2 cnt <= 2 SCAN_TOP places are written
+    const bool live = threadIdx.x < cnt;
+    const uint64_t me = live ? cur[threadIdx.x] : 0;
+    const unsigned mark = live ? diff_mark(w, level, me) : 0;
+    const unsigned long long bl = __ballot(mark & 1), br = __ballot(mark & 2);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const unsigned before = __popcll(bl & below) + __popcll(br & below);
+    if (lane == 0) wave_tot[wave] = __popcll(bl) + __popcll(br);
+    __syncthreads();
+    unsigned p = before, total = 0;
+    for (unsigned v = 0; v < SCAN_TOP / 64; ++v) {
+      if (v < wave) p += wave_tot[v];
+      total += wave_tot[v];
+    }
+    const unsigned limit = diff_limit(w, level - 1);
+    if ((mark & 1) && p < limit) next[p] = 2 * me;
+    p += mark & 1;
+    if ((mark & 2) && p < limit) next[p] = 2 * me + 1;
+    if (total > limit) more = 1;  // property 2: a cut at any level
+    cnt = total < limit ? total : limit;
+    --level;
+    __syncthreads();  // next[] is read by other threads, wave_tot is written again
+    if (cnt == 0) level = 0;  // nothing differs in range: the answer is empty
+  }
+  if (level == 0) {  // cnt <= min(cap, 2 SCAN_TOP) keys in frontier 0: their leaves
+    for (unsigned i = threadIdx.x; i < cnt; i += SCAN_TOP) {
+      const uint64_t key = fr[0][i];
+      w.frontier[0][i] = key;
+      diff_leaf(w, key, i);
+    }
+  } else {           // hand over at `level`: marks and totals of its frontier, as a step launch would have left them
+    const uint64_t* cur = fr[level & 1];
+    for (unsigned base = 0; base < cnt; base += SCAN_TOP) {
+      const unsigned i = base + threadIdx.x;  // the 64 nodes of a wave lie in one SCAN_BLOCK: one atomic per wave
+      const unsigned mark = i < cnt ? diff_mark(w, level, cur[i]) : 0;
+      if (i < cnt) {
+        w.frontier[level & 1][i] = cur[i];
+        w.marks[level & 1][i] = (uint8_t)mark;
+      }
+      const unsigned kept = scan_wave_sum((unsigned)__popc(mark));
+      if (lane == 0 && kept) atomicAdd(&w.tot[(size_t)level * w.blocks + i / SCAN_BLOCK], kept);
+    }
+  }
+  if (threadIdx.x == 0) {
+    w.hdr->n = level == 0 ? cnt : 0;
+    w.hdr->more = more;
+    w.hdr->start = level;
+    if (level) w.cnt[level] = cnt;
+  }
+}
+// One step, level -> level - 1, one thread per frontier node: tree_scan_step_kernel with diff_mark / diff_leaf (256
+// nodes per block, a mark byte per node, one atomic per wave and block for the block totals, each block sums the
+// totals in front of it).
+__global__ void __launch_bounds__(SCAN_BLOCK)
+tree_diff_step_kernel(DiffWork w, unsigned level) {
+  __shared__ unsigned wave_tot[SCAN_BLOCK / 64];
+  __shared__ unsigned wave_sum[2][SCAN_BLOCK / 64];
+  if (level > w.hdr->start) return;  // the top kernel has walked this level
+  const unsigned cnt = w.cnt[level];
+  const unsigned b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (b * SCAN_BLOCK >= cnt) return;  // surplus block (cnt == 0: cnt[level - 1] keeps the 0 it was cleared to)
+  const unsigned live_blocks = (cnt + SCAN_BLOCK - 1) / SCAN_BLOCK;
+  const unsigned* tot = w.tot + (size_t)level * w.blocks;
+  unsigned front = 0, all = 0;
+  for (unsigned j = threadIdx.x; j < (b == 0 ? live_blocks : b); j += SCAN_BLOCK) {
+    const unsigned t = tot[j];
+    if (j < b) front += t;
+    all += t;
+  }
+  front = scan_wave_sum(front);
+  all = scan_wave_sum(all);
+  const unsigned i = b * SCAN_BLOCK + threadIdx.x;
+  const bool live = i < cnt;
+  const uint64_t me = live ? w.frontier[level & 1][i] : 0;
+  const unsigned mark = live ? w.marks[level & 1][i] : 0;
+  const unsigned long long bl = __ballot(mark & 1), br = __ballot(mark & 2);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned p = __popcll(bl & below) + __popcll(br & below);
+  if (lane == 0) {
+    wave_tot[wave] = __popcll(bl) + __popcll(br);
+    wave_sum[0][wave] = front;
+    wave_sum[1][wave] = all;
+  }
+  __syncthreads();
+  front = all = 0;
+  for (unsigned v = 0; v < SCAN_BLOCK / 64; ++v) {
+    if (v < wave) p += wave_tot[v];
+    front += wave_sum[0][v];
+    all += wave_sum[1][v];
+  }
+  unsigned wave_first = front;  // position of the wave's first child: its at most 128 children lie in two SCAN_BLOCKs
+  for (unsigned v = 0; v < wave; ++v) wave_first += wave_tot[v];
+  const unsigned bucket = wave_first / SCAN_BLOCK;
+  p += front;
+  const unsigned limit = diff_limit(w, level - 1);
+  uint64_t* next = w.frontier[(level - 1) & 1];
+  unsigned kept_lo = 0, kept_hi = 0;  // kept grandchildren whose parent lies in `bucket` / in the one behind it
+#pragma unroll
+  for (unsigned side = 0; side < 2; ++side) {
+    if (mark & (1u << side)) {
+      if (p < limit) {  // the cut (property 2)
+        const uint64_t child = 2 * me + side;
+        next[p] = child;
+        if (level > 1) {
+          const unsigned m = diff_mark(w, level - 1, child);
+          w.marks[(level - 1) & 1][p] = (uint8_t)m;
+          if (p / SCAN_BLOCK == bucket) kept_lo += (unsigned)__popc(m); else kept_hi += (unsigned)__popc(m);
+        } else {
+          diff_leaf(w, child, p);
+        }
+      }
+      ++p;
+    }
+  }
+  kept_lo = scan_wave_sum(kept_lo);
+  kept_hi = scan_wave_sum(kept_hi);
+  if (lane == 0 && level > 1) {  // one atomic per wave and bucket
+    unsigned* into = w.tot + (size_t)(level - 1) * w.blocks + bucket;
+    if (kept_lo) atomicAdd(into, kept_lo);
+    if (kept_hi) atomicAdd(into + 1, kept_hi);
+  }
+  if (b == 0 && threadIdx.x == 0) {
+    const unsigned kept = all < limit ? all : limit;
+    if (all > limit) w.hdr->more = 1;
+    if (level > 1) w.cnt[level - 1] = kept; else w.hdr->n = kept;
+  }
+}
+
 struct SparseTree {
   unsigned height = 0;
   uint64_t empty_leaf[4] = {0, 0, 0, 0};
@@ -1582,6 +1843,194 @@ int sp_tree_scan(int tree, uint64_t lo, uint64_t hi, size_t capacity, uint64_t* 
     }
   }
   tl_mark("scan: results on the host");
+  *n = (size_t)h.n;
+  *more = h.more ? 1 : 0;
+  return SP_OK;
+}
+
+// ---- sp_tree_clone (include/starkperp.h): a second handle on the same tree - device copies, nothing hashed.  The
+// source's mutex is held from start to end.  The copies are enqueued on the SOURCE's stream, behind the insert kernel of
+// its last commit (which nobody has waited for), and waited for before the call returns.  Nothing of the clone is
+// registered before every allocation and copy has succeeded: a failure leaves no handle and the source as it was. ----
+int sp_tree_clone(int tree, int* clone) {
+  SP_REQUIRE_READY();
+  if (!clone) { set_error("sp_tree_clone: null argument"); return SP_ERR_BAD_ARGUMENT; }
+  TimelineScope timeline("sp_tree_clone");
+  TreeScope ts;
+  int rc = ts.open(tree);
+  if (rc != SP_OK) return rc;
+  SparseTree& s = *ts.t;
+  auto t = std::make_shared<SparseTree>();
+  t->height = s.height;
+  t->ctx_index = s.ctx_index;
+  std::memcpy(t->empty_leaf, s.empty_leaf, 32);
+  t->has_root = s.has_root;
+  std::memcpy(t->root, s.root, 32);
+  // stream, work buffer, staging buffer: the clone's own, made by its first call as a created tree's are; the per-level
+  // constant points are recomputed by its first update (cpts_state 0)
+  if (s.table.ptr || s.d_entries) {  // a tree that was never updated has neither: its clone is a fresh tree, no device work
+    TreeSlot* table = nullptr;
+    unsigned long long* counter = nullptr;
+    hipError_t e = hipSuccess;
+    const char* what = "hipMalloc (the clone's table)";
+    if (s.table.ptr) e = hipMalloc(&table, s.slots * sizeof(TreeSlot));
+    if (e == hipSuccess && s.d_entries) {
+      what = "hipMalloc (the clone's entry counter)";
+      e = hipMalloc(&counter, sizeof(unsigned long long));
+    }
+    if (e == hipSuccess && table) {
+      what = "hipMemcpyAsync (table, device to device)";
+      e = hipMemcpyAsync(table, s.table.ptr, s.slots * sizeof(TreeSlot), hipMemcpyDeviceToDevice, s.stream);
+    }
+    if (e == hipSuccess && counter) {
+      what = "hipMemcpyAsync (entry counter, device to device)";
+      e = hipMemcpyAsync(counter, s.d_entries, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s.stream);
+    }
+    tl_mark("clone: copies enqueued");
+    // also on a failure: a copy that did get onto the stream writes into what is freed below
+    const hipError_t waited = hipStreamSynchronize(s.stream);
+    if (e == hipSuccess && waited != hipSuccess) {
+      what = "hipStreamSynchronize (the source's stream)";
+      e = waited;
+    }
+    if (e != hipSuccess) {
+      if (table) (void)hipFree(table);
+      if (counter) (void)hipFree(counter);
+      return hip_fail(e, what);
+    }
+    tl_mark("clone: copies done");
+    t->table.ptr = table;
+    t->table.bytes = table ? s.slots * sizeof(TreeSlot) : 0;
+    t->slots = table ? s.slots : 0;
+    t->d_entries = counter;
+    t->entries = s.entries;
+  }
+  ctx_lock lk(global_mu());
+  const int id = g_next_tree++;
+  g_trees.emplace(id, t);
+  *clone = id;
+  return SP_OK;
+}
+
+// ---- sp_tree_diff (include/starkperp.h): where two trees differ, in order, in pages - the descent of
+// tree_diff_top_kernel / tree_diff_step_kernel.  Both tree mutexes from start to end, taken in ascending handle order
+// (as sp_state_batch takes them: diff(a, b) beside diff(b, a) cannot block); the work runs on the stream and in the work
+// buffer of the lower handle, behind a wait for the other tree's stream (the insert kernel of its last commit may
+// still be in flight); the library lock only inside tree_empty_roots.  One wait, at the end. ----
+int sp_tree_diff(int tree_a, int tree_b, uint64_t lo, uint64_t hi, size_t capacity, uint64_t* keys, uint64_t* leaves_a,
+                 uint64_t* leaves_b, size_t* n, int* more) {
+  SP_REQUIRE_READY();
+  if (!keys || !leaves_a || !leaves_b || !n || !more) { set_error("sp_tree_diff: null argument"); return SP_ERR_BAD_ARGUMENT; }
+  if (capacity == 0) { set_error("sp_tree_diff: capacity must be at least 1"); return SP_ERR_BAD_ARGUMENT; }
+  if (lo > hi) { set_error("sp_tree_diff: lo above hi"); return SP_ERR_BAD_ARGUMENT; }
+  if (tree_a == tree_b) { set_error("sp_tree_diff: the same tree handle twice"); return SP_ERR_BAD_ARGUMENT; }
+  TimelineScope timeline("sp_tree_diff");
+  TreeScope first, second;
+  const bool a_first = tree_a < tree_b;
+  int rc = first.open(a_first ? tree_a : tree_b);
+  if (rc != SP_OK) return rc;
+  rc = second.open(a_first ? tree_b : tree_a);
+  if (rc != SP_OK) return rc;
+  SparseTree& A = a_first ? *first.t : *second.t;
+  SparseTree& B = a_first ? *second.t : *first.t;
+  SparseTree& t = *first.t;      // whose stream, work buffer and staging buffer serve the call
+  SparseTree& other = *second.t;
+  if (A.ctx_index != B.ctx_index) { set_error("sp_tree_diff: the two trees live on different contexts"); return SP_ERR_BAD_ARGUMENT; }
+  if (A.height != B.height) { set_error("sp_tree_diff: the two trees differ in height"); return SP_ERR_BAD_ARGUMENT; }
+  if (std::memcmp(A.empty_leaf, B.empty_leaf, 32) != 0) {
+    set_error("sp_tree_diff: the two trees differ in their empty leaf");
+    return SP_ERR_BAD_ARGUMENT;
+  }
+  const unsigned height = A.height;
+  if (height < 64 && (hi >> height) != 0) { set_error("sp_tree_diff: hi out of range for height"); return SP_ERR_BAD_ARGUMENT; }
+  std::vector<uint64_t> emp;
+  rc = tree_empty_roots(A, emp);
+  if (rc != SP_OK) return rc;
+  const uint64_t* empty_root = &emp[4 * (size_t)height];
+  // a tree without a committed update stands at the empty root, whether its table exists (a rejected first update) or not
+  if (std::memcmp(A.has_root ? A.root : empty_root, B.has_root ? B.root : empty_root, 32) == 0) {
+    *n = 0;  // equal roots: the frontier of level `height` is empty, no launch
+    *more = 0;
+    return SP_OK;
+  }
+  const size_t cap = capacity < SP_TREE_DIFF_MAX ? capacity : SP_TREE_DIFF_MAX;
+  const size_t wide = cap + 2;  // what a frontier above level 0 keeps (diff_limit)
+  const size_t blocks = (wide + SCAN_BLOCK - 1) / SCAN_BLOCK;
+  // work buffer: empty roots | header, keys (= frontier 0), leaves of A, leaves of B: what goes back, one piece |
+  // frontier 1 | marks 0 | marks 1 | the zeroed slot, cnt[65], tot[height + 1][blocks]: cleared once
+  const size_t emp_bytes = ((size_t)height + 1) * 32, out_bytes = sizeof(ScanHeader) + wide * 8 + 2 * cap * 32;
+  const size_t f1_off = emp_bytes + out_bytes, m_off = f1_off + wide * 8, z_off = (m_off + 2 * wide + 15) & ~(size_t)15;
+  const size_t none_bytes = 64;  // one TreeSlot, 16-byte aligned
+  const size_t z_bytes = none_bytes + (65 + ((size_t)height + 1) * blocks) * sizeof(unsigned);
+  SP_HIP(t.buf.reserve(z_off + z_bytes + 64));
+  char* b = (char*)t.buf.ptr;
+  DiffWork w;
+  w.tab[0] = A.has_root ? A.table.ptr : nullptr;  // (a table without a root holds nothing)
+  w.tab[1] = B.has_root ? B.table.ptr : nullptr;
+  w.mask[0] = w.tab[0] ? A.slots - 1 : 0;
+  w.mask[1] = w.tab[1] ? B.slots - 1 : 0;
+  w.none = (const TreeSlot*)(b + z_off);
+  w.emp = (const uint64_t*)b;
+  w.lo = lo;
+  w.hi = hi;
+  w.cap = (unsigned)cap;
+  w.blocks = (unsigned)blocks;
+  w.hdr = (ScanHeader*)(b + emp_bytes);
+  w.frontier[0] = (uint64_t*)(b + emp_bytes + sizeof(ScanHeader));
+  w.leaves[0] = w.frontier[0] + wide;
+  w.leaves[1] = w.leaves[0] + 4 * cap;
+  w.frontier[1] = (uint64_t*)(b + f1_off);
+  w.marks[0] = (uint8_t*)(b + m_off);
+  w.marks[1] = w.marks[0] + wide;
+  w.cnt = (unsigned*)(b + z_off + none_bytes);
+  w.tot = w.cnt + 65;
+  hipStream_t st = t.stream;
+  // the other tree's last commit (its insert kernel, the rehash of a growth) may still be in flight on ITS stream; the
+  // call is synchronous and holds both mutexes, so nothing of either tree starts before the reads below are done
+  SP_HIP(hipStreamSynchronize(other.stream));
+  tl_mark("diff: work buffer ready");
+  const bool whole = StagedTrip::fits(emp_bytes + out_bytes);
+  StagedTrip trip(t.hbuf, whole ? emp_bytes + out_bytes : emp_bytes + sizeof(ScanHeader), st);
+  char* const stage = trip.stage;
+  SP_HIP(trip.up(b, {{emp.data(), emp_bytes}}));
+  SP_HIP(hipMemsetAsync(b + z_off, 0, z_bytes, st));
+  hipLaunchKernelGGL(tree_diff_top_kernel, dim3(1), dim3(SCAN_TOP), 0, st, w, height);
+  // as in sp_tree_scan: the top kernel hands over at level height - 11 or below, and never when cap + 2 <= SCAN_TOP
+  if (wide > SCAN_TOP) {
+    for (unsigned level = height > 11 ? height - 11 : 0; level >= 1; --level) {
+      hipLaunchKernelGGL(tree_diff_step_kernel, dim3((unsigned)blocks), dim3(SCAN_BLOCK), 0, st, w, level);
+    }
+  }
+  SP_HIP(hipGetLastError());
+  tl_mark("diff: kernels enqueued");
+  if (timeline.mine) {  // diagnostics only, as in sp_tree_witness
+    SP_HIP(hipStreamSynchronize(st));
+    tl_mark("diff: kernels done");
+  }
+  ScanHeader h;
+  h.n = 0;
+  h.more = 0;
+  h.start = 0;
+  if (stage && whole) {  // the whole page in one copy; what the header counts goes on to the caller
+    SP_HIP(trip.down(w.hdr, {{&h, sizeof(h)}, {keys, wide * 8}, {leaves_a, cap * 32}, {leaves_b, cap * 32}}));
+    SP_HIP(hipStreamSynchronize(st));
+    trip.finish({{&h, sizeof(h)}});
+    if (h.n > cap) { set_error("sp_tree_diff: inconsistent count"); return SP_ERR_HIP; }
+    trip.finish({{nullptr, sizeof(h)}, {keys, h.n * 8}, {nullptr, (wide - h.n) * 8}, {leaves_a, h.n * 32},
+                 {nullptr, (cap - h.n) * 32}, {leaves_b, h.n * 32}});
+  } else {  // the header first, then exactly n keys and two runs of n leaves
+    SP_HIP(hipMemcpyAsync(stage ? (void*)(stage + emp_bytes) : (void*)&h, w.hdr, sizeof(h), hipMemcpyDeviceToHost, st));
+    SP_HIP(hipStreamSynchronize(st));
+    if (stage) std::memcpy(&h, stage + emp_bytes, sizeof(h));
+    if (h.n > cap) { set_error("sp_tree_diff: inconsistent count"); return SP_ERR_HIP; }
+    if (h.n) {
+      SP_HIP(hipMemcpyAsync(keys, w.frontier[0], h.n * 8, hipMemcpyDeviceToHost, st));
+      SP_HIP(hipMemcpyAsync(leaves_a, w.leaves[0], h.n * 32, hipMemcpyDeviceToHost, st));
+      SP_HIP(hipMemcpyAsync(leaves_b, w.leaves[1], h.n * 32, hipMemcpyDeviceToHost, st));
+      SP_HIP(hipStreamSynchronize(st));
+    }
+  }
+  tl_mark("diff: results on the host");
   *n = (size_t)h.n;
   *more = h.more ? 1 : 0;
   return SP_OK;

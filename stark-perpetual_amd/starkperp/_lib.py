@@ -132,6 +132,9 @@ _SIGNATURES = {
     "sp_tree_scan": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t]
                      + [ctypes.c_void_p] * 4),
     "sp_tree_table_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "sp_tree_clone": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p]),
+    "sp_tree_diff": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t]
+                     + [ctypes.c_void_p] * 5),
     "sp_tree_destroy": (ctypes.c_int, [ctypes.c_int]),
     "sp_ecdsa_verify_batch": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_size_t]),
     "sp_ecdsa_verify_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]),

@@ -384,6 +384,34 @@ def tree_scan(handle, lo, hi, capacity):
     return keys[:count.value], leaves[:count.value], bool(more.value)
 
 
+def tree_clone(handle):
+    """A second handle holding the same tree (sp_tree_clone): the node table is copied on the device, nothing is hashed.
+    Returns the new integer handle; the caller destroys it (state.LibrarySparseTree.clone wraps it)."""
+    handle = getattr(handle, "_handle", handle)
+    out = ctypes.c_int()
+    _lib.check(_lib.ensure_init().sp_tree_clone(handle, ctypes.byref(out)), "sp_tree_clone")
+    return out.value
+
+
+TREE_DIFF_MAX = TREE_SCAN_MAX  # SP_TREE_DIFF_MAX: the largest page of one sp_tree_diff call
+
+
+def tree_diff(a, b, lo, hi, capacity):
+    """One page of the ordered diff (sp_tree_diff) of the trees behind `a` and `b` (state.LibrarySparseTree or integer
+    handles): the first `capacity` keys k, lo <= k <= hi inclusive, whose leaf in a differs from the leaf in b.
+    Returns (keys uint64[n] ascending, leaves_a uint64[n, 4], leaves_b uint64[n, 4], more bool); a key one tree does
+    not hold reads as the empty leaf there; more: further differing keys exist in the range, resume with
+    lo = keys[-1] + 1."""
+    a, b = getattr(a, "_handle", a), getattr(b, "_handle", b)
+    cap = max(min(int(capacity), TREE_DIFF_MAX), 1)
+    keys = np.zeros(cap, dtype=np.uint64)
+    leaves_a, leaves_b = np.zeros((cap, 4), dtype=np.uint64), np.zeros((cap, 4), dtype=np.uint64)
+    count, more = ctypes.c_size_t(), ctypes.c_int()
+    _lib.check(_lib.ensure_init().sp_tree_diff(a, b, lo, hi, capacity, _ptr(keys), _ptr(leaves_a), _ptr(leaves_b),
+                                               ctypes.byref(count), ctypes.byref(more)), "sp_tree_diff")
+    return keys[:count.value], leaves_a[:count.value], leaves_b[:count.value], bool(more.value)
+
+
 def tree_table_size(handle):
     """(entries, slots) of the tree's node table as it stands (sp_tree_table_size): slots in use - it never shrinks -
     and the slot count."""

@@ -240,6 +240,85 @@ class SparseMerkleTree:
             raise ValueError("the restored tree's root is not the snapshot's")
         return tree
 
+    def clone(self) -> "SparseMerkleTree":
+        """A second tree holding the same state, the host twin of sp_tree_clone: the facts store is copied, nothing is
+        hashed, and updating either tree afterwards leaves the other untouched."""
+        out = object.__new__(type(self))
+        out.height, out.hash_many = self.height, self.hash_many
+        out.facts, out.empties, out.root = dict(self.facts), list(self.empties), self.root
+        return out
+
+    def diff(self, other: "SparseMerkleTree", lo: int = 0, hi: Optional[int] = None, capacity: Optional[int] = None):
+        """Ordered diff, the host twin of sp_tree_diff: the first `capacity` (None: all) keys k, lo <= k <= hi inclusive,
+        whose leaf here differs from the leaf in `other` (same height and empty leaf), as [(key, leaf_self, leaf_other)]
+        ascending, and `more`.  `scan`'s descent from the two roots through the two facts stores: the frontier of a level
+        holds the nodes whose key interval meets [lo, hi] and whose VALUES differ - equal nodes are equal subtrees, a
+        node that differs has a differing leaf below it - with the same cut (capacity + 2 above level 0, capacity at
+        level 0, a cut at any level means `more`).  No hash."""
+        assert self.height == other.height and self.empties[0] == other.empties[0], \
+            "diff needs two trees of one height and one empty leaf"
+        top = (1 << self.height) - 1
+        hi = top if hi is None else hi
+        assert 0 <= lo <= hi <= top, "diff range out of order or out of range for height"
+        assert capacity is None or capacity >= 1, "capacity must be at least 1"
+        more = False
+        frontier = [(0, self.root, other.root)] if self.root != other.root else []
+        for level in range(self.height, 0, -1):
+            below = []
+            for idx, mine, theirs in frontier:
+                for child, a, b in zip((2 * idx, 2 * idx + 1), self._children(mine, level), other._children(theirs, level)):
+                    first = child << (level - 1)
+                    if a != b and first <= hi and first | ((1 << (level - 1)) - 1) >= lo:
+                        below.append((child, a, b))
+            limit = None if capacity is None else capacity + 2 if level > 1 else capacity
+            if limit is not None and len(below) > limit:
+                more, below = True, below[:limit]
+            frontier = below
+        return frontier, more
+
+    def diff_items(self, other, lo: int = 0, hi: Optional[int] = None, page: int = 65536):
+        """Generator over every (key, leaf_self, leaf_other) of `diff`'s range, one diff of `page` keys at a time."""
+        return _diff_pages(self, other, lo, hi, page)
+
+    def delta(self, base: "SparseMerkleTree", page: int = 1 << 18) -> dict:
+        """What turns `base` into this tree: {"height", "empty_leaf", "base_root", "root", "keys", "leaves"} - the keys
+        (ascending) where this tree differs from `base`, with THIS tree's leaves.  `base.apply_delta` of it reaches this
+        tree's root: an incremental snapshot."""
+        triples = list(self.diff_items(base, page=page))
+        return {"height": self.height, "empty_leaf": self.empties[0], "base_root": base.root, "root": self.root,
+                "keys": [k for k, _, _ in triples], "leaves": [v for _, v, _ in triples]}
+
+    def apply_delta(self, delta: dict, chunk: int = 1 << 18):
+        """Writes the leaves of a `delta` (of either tree class) in ascending chunks.  ValueError, with nothing written,
+        when this tree's root is not the delta's base_root or its height or empty leaf differ; ValueError when the root
+        that results is not delta["root"] - the tree then HOLDS the delta's leaves.  Returns (old_root, new_root)."""
+        _check_delta(self, self.empties[0], delta)
+        old_root = self.root
+        keys, leaves = _snapshot_ints(delta)
+        for at in range(0, len(keys), chunk):
+            self.update(dict(zip(keys[at:at + chunk], leaves[at:at + chunk])))
+        if self.root != int(delta["root"]):
+            raise ValueError("the tree's root after the delta is not the delta's")
+        return old_root, self.root
+
+
+def _diff_pages(tree, other, lo, hi, page):
+    """The pages of tree.diff(other, lo, hi, page) one after the other, as _scan_pages pages a scan."""
+    while True:
+        triples, more = tree.diff(other, lo, hi, page)
+        yield from triples
+        if not more:
+            return
+        lo = triples[-1][0] + 1
+
+
+def _check_delta(tree, empty_leaf, delta):
+    """What apply_delta checks BEFORE it writes: the delta was taken for a tree of this shape standing at this root."""
+    if int(delta["height"]) != tree.height or int(delta["empty_leaf"]) != empty_leaf:
+        raise ValueError("the delta was taken from a tree of another height or empty leaf")
+    if tree.root != int(delta["base_root"]):
+        raise ValueError("the tree's root is not the delta's base root")
+
 
 def _scan_pages(tree, lo, hi, page):
     """The pages of tree.scan(lo, hi, page) one after the other: `more` says whether to go on, the next page starts
@@ -617,6 +696,80 @@ class LibrarySparseTree:
         grows, and keeps the paths of leaves that were set back to the empty leaf)."""
         return self.restore(self.snapshot(), context=self.context)
 
+    def clone(self) -> "LibrarySparseTree":
+        """A second tree holding the same state on the same context (sp_tree_clone): one device copy of the node table,
+        nothing hashed; updating or closing either tree afterwards leaves the other untouched.  A checkpoint to roll
+        back to, a fork to try a batch on, a base to `diff` against."""
+        from . import batch_np
+        out = object.__new__(type(self))
+        out._lib, out._ct = self._lib, self._ct
+        out.height, out.empty_leaf, out.context = self.height, self.empty_leaf, self.context
+        out._handle = None
+        out._handle = batch_np.tree_clone(self)
+        return out
+
+    def diff(self, other: "LibrarySparseTree", lo: int = 0, hi: Optional[int] = None, capacity: Optional[int] = None):
+        """As SparseMerkleTree.diff, one page in one call (sp_tree_diff): ([(key, leaf_self, leaf_other)] ascending,
+        more).  capacity None: the largest page of a call (batch_np.TREE_DIFF_MAX keys); `diff_items` pages through any
+        number.  The page is taken under both trees' mutexes: it describes a batch boundary of both."""
+        from . import batch_np
+        assert isinstance(other, LibrarySparseTree), "diff compares two trees the library keeps"
+        top = (1 << self.height) - 1
+        hi = top if hi is None else hi
+        assert 0 <= lo <= hi <= top, "diff range out of order or out of range for height"
+        assert capacity is None or capacity >= 1, "capacity must be at least 1"
+        keys, mine, theirs, more = batch_np.tree_diff(self, other, lo, hi,
+                                                      batch_np.TREE_DIFF_MAX if capacity is None else capacity)
+        if not len(keys):
+            return [], more
+        return list(zip(keys.tolist(), batch_np.ints_from_felts(mine), batch_np.ints_from_felts(theirs))), more
+
+    def diff_items(self, other, lo: int = 0, hi: Optional[int] = None, page: int = 65536):
+        """Generator over every (key, leaf_self, leaf_other) of `diff`'s range, one sp_tree_diff call of `page` keys at
+        a time; an update of either tree between two pages shows in the later ones."""
+        return _diff_pages(self, other, lo, hi, page)
+
+    def delta(self, base: "LibrarySparseTree", page: int = 1 << 18) -> dict:
+        """What turns `base` into this tree: {"height", "empty_leaf", "base_root", "root", "keys" uint64[n] ascending,
+        "leaves" uint64[n, 4]} - the keys where this tree differs from `base`, with THIS tree's leaves, read in pages of
+        `page` keys.  An incremental snapshot: `base.apply_delta` of it reaches this tree's root.  The caller keeps
+        updates away from both trees while it is taken; both roots are read first and `apply_delta` compares them."""
+        import numpy as np
+        from . import batch_np
+        root, base_root, lo, top = self.root, base.root, 0, (1 << self.height) - 1
+        keys, leaves = [np.zeros(0, dtype=np.uint64)], [np.zeros((0, 4), dtype=np.uint64)]
+        while True:
+            k, mine, _, more = batch_np.tree_diff(self, base, lo, top, page)
+            keys.append(k)
+            leaves.append(mine)
+            if not more:
+                break
+            lo = int(k[-1]) + 1
+        return {"height": self.height, "empty_leaf": self.empty_leaf, "base_root": base_root, "root": root,
+                "keys": np.concatenate(keys), "leaves": np.concatenate(leaves)}
+
+    def apply_delta(self, delta: dict, chunk: int = 1 << 18):
+        """Writes the leaves of a `delta` (of either tree class) through `update_arrays` in ascending chunks of `chunk`.
+        ValueError, with nothing written, when this tree's root is not the delta's base_root or its height or empty leaf
+        differ; ValueError when the root that results is not delta["root"] - the tree then HOLDS the delta's leaves (a
+        `clone` taken before is the way back).  Returns (old_root, new_root)."""
+        import numpy as np
+        from . import batch_np
+        _check_delta(self, self.empty_leaf, delta)
+        old_root = self.root
+        keys, leaves = delta["keys"], delta["leaves"]
+        if not hasattr(leaves, "shape"):
+            leaves = batch_np.felts_from_ints(leaves) if len(leaves) else np.zeros((0, 4), dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        assert keys.ndim == 1 and leaves.shape == (keys.shape[0], 4) and (keys[1:] > keys[:-1]).all(), \
+            "delta keys must be strictly increasing, one leaf each"
+        for at in range(0, keys.shape[0], chunk):
+            self.update_arrays(keys[at:at + chunk], leaves[at:at + chunk])
+        new_root = self.root
+        if new_root != int(delta["root"]):
+            raise ValueError("the tree's root after the delta is not the delta's")
+        return old_root, new_root
+
     @property
     def entries(self) -> int:
         """Slots of the node table in use (sp_tree_table_size): it never shrinks."""
@@ -839,6 +992,33 @@ class SharedState:
             raise
         out.positions, out.orders = trees
         return out
+
+    def fork(self) -> "SharedState":
+        """A second state standing where this one stands: both trees cloned (sp_tree_clone, or the host twins' stores
+        copied), nothing mutable shared.  A batch tried on the fork leaves this state untouched."""
+        out = object.__new__(type(self))
+        out._position_hashes, out._hash_many = self._position_hashes, self._hash_many
+        out.positions = self.positions.clone()
+        try:
+            out.orders = self.orders.clone()
+        except BaseException:
+            if hasattr(out.positions, "close"):
+                out.positions.close()
+            raise
+        return out
+
+    def delta(self, base: "SharedState") -> dict:
+        """{"positions": ..., "orders": ...}: the `delta` of both trees against `base`'s, taken between two batches -
+        what the batches since `base` changed, not what the trees hold."""
+        return {"positions": self.positions.delta(base.positions), "orders": self.orders.delta(base.orders)}
+
+    def apply_delta(self, d: dict):
+        """Applies a `delta` (of either route) to both trees.  ValueError with NEITHER tree written when one of them does
+        not stand at its delta's base root; then as the trees' apply_delta.  Returns ((old_pos_root, new_pos_root),
+        (old_ord_root, new_ord_root))."""
+        for tree, part in ((self.positions, "positions"), (self.orders, "orders")):
+            _check_delta(tree, tree.empty_leaf if hasattr(tree, "empty_leaf") else tree.empties[0], d[part])
+        return self.positions.apply_delta(d["positions"]), self.orders.apply_delta(d["orders"])
 
     def close(self):
         """Releases the library-side trees (no-op for the host-bookkeeping variant)."""
