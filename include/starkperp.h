@@ -25,7 +25,7 @@
  *     host-pointer batches that carry no shared state - sp_pedersen_batch, sp_pedersen_chains,
  *     sp_pedersen_chains_ragged, sp_merkle_fold_paths, sp_merkle_verify_paths, sp_merkle_verify_update,
  *     sp_ecdsa_verify_batch (per-signature ladder), sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch,
- *     sp_public_key_batch -
+ *     sp_public_key_batch, sp_felt_sqrt_batch, sp_stark_key_y_batch -
  *     run on one of 16 host lanes (own stream, own staging buffer) and hold the lock only while a
  *     kernel is enqueued: calls from different threads overlap on the device - on the devices, after
  *     sp_init_devices - (a seventeenth concurrent caller waits for a lane).  Keyed verification runs on a lane too and holds the
@@ -90,12 +90,14 @@ int sp_init(int device, int window_bits);
 /* Several devices in one process (the SURVEY 8(b) shape `sp_init(n_devices, device_ids)`): one context - its own
  * window tables - per entry of device_ids; context 0 is the PRIMARY.  What runs where:
  *   - the stateless batches run on ANY context: sp_pedersen_batch, sp_ecdsa_verify_batch (ladder),
- *     sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch, sp_public_key_batch take the context of the host lane
+ *     sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch, sp_public_key_batch, sp_felt_sqrt_batch,
+ *     sp_stark_key_y_batch take the context of the host lane
  *     they are handed (lanes go round-robin over the contexts, so concurrent host threads spread over the
  *     devices), and one call of sp_pedersen_batch / sp_ecdsa_verify_batch with 16384 items or more is cut into
  *     one contiguous slice per context, the slices running side by side on host threads of the library; sp_pedersen_batch_dev, sp_pedersen_chains_dev, sp_pedersen_chains_ragged_dev, sp_merkle_fold_paths_dev, sp_merkle_build_dev, sp_merkle_forest_dev,
- *     sp_commit_rows_dev, sp_ecdsa_verify_batch_dev, sp_ecdsa_sign_batch_dev, sp_ecdsa_sign_rfc6979_batch_dev and
- *     sp_public_key_batch_dev run on the device their pointers live on (the stream
+ *     sp_commit_rows_dev, sp_ecdsa_verify_batch_dev, sp_ecdsa_sign_batch_dev, sp_ecdsa_sign_rfc6979_batch_dev,
+ *     sp_public_key_batch_dev, sp_felt_sqrt_batch_dev and sp_stark_key_y_batch_dev run on the device their pointers
+ *     live on (the stream
  *     must belong to that device);
  *   - everything with state - persistent trees, key tables, the prover entry points (twiddle tables, witness
  *     scratch) and the remaining host-pointer calls - stays on the primary device.
@@ -121,7 +123,8 @@ const char* sp_build_info(void);
 
 /* Measurement aid: between sp_profile_begin and sp_profile_end every launch of the dominant kernel
  * (ped_accumulate_kernel) is bracketed by HIP events on the stream it is launched on; _end returns
- * the summed kernel time, the number of launches and the number of hashes they processed. */
+ * the summed kernel time, the number of launches and the number of hashes they processed.  The launches of
+ * sp_felt_sqrt_batch* and sp_stark_key_y_batch* are bracketed the same way (units: items). */
 int sp_profile_begin(size_t max_launches);
 int sp_profile_end(double* total_ms, uint64_t* launches, uint64_t* units);
 
@@ -558,6 +561,29 @@ int sp_ecdsa_sign_rfc6979_batch_dev(const uint64_t* z, const uint64_t* d, const 
 int sp_public_key_batch(const uint64_t* d, uint64_t* qx, uint64_t* qy, uint8_t* status, size_t n);
 /* The same on device pointers (qy, status may be NULL; outputs of a rejected item are left as they were). */
 int sp_public_key_batch_dev(const uint64_t* d, uint64_t* qx, uint64_t* qy, uint8_t* status, size_t n, void* stream);
+
+/* ---- square roots mod p, x-only Stark keys ---------------------------------------------------------- */
+/* per-item status of sp_felt_sqrt_batch* and sp_stark_key_y_batch* */
+#define SP_SQRT_OK 0
+#define SP_SQRT_NON_RESIDUE 1   /* no root: get_y_coordinate raises InvalidPublicKeyError, is_valid_stark_key is False */
+#define SP_SQRT_OUT_OF_RANGE 2  /* the input is not in [0, p) */
+/* sqrt_mod(a, FIELD_PRIME) math_utils.py:43-47 with is_quad_residue math_utils.py:36-40 as its status: root[i] is the
+ * smaller of the two roots of a[i] when status[i] is SP_SQRT_OK (a = 0: root 0, OK, as sympy counts it) and is left as
+ * it was otherwise.  status is required and written for every item, exactly.  root == NULL asks for the status bytes
+ * alone (the Legendre symbol: no root is extracted).  n == 0 is legal.  a and root must not overlap (equal pointers:
+ * SP_ERR_BAD_ARGUMENT; lanes past the end of the batch redo its last item).  A fixed number of field operations for
+ * every in-range non-zero input, residue or not (2 338 against up to 18 528 squarings of Tonelli-Shanks for this prime,
+ * whose 2-part has order 2^192): csrc/fp29.hpp fe_sqrt.  The first root call of a context builds and uploads its
+ * 204 KiB of tables under the library lock (an allocation: not capturable into a hipGraph - call once before a
+ * capture); sp_shutdown frees them; sp_table_bytes does not count them.  The host call runs on a host lane. */
+int sp_felt_sqrt_batch(const uint64_t* a, uint64_t* root, uint8_t* status, size_t n);
+/* The same on device pointers, on the device they live on: enqueued on `stream`, nothing waited for. */
+int sp_felt_sqrt_batch_dev(const uint64_t* a, uint64_t* root, uint8_t* status, size_t n, void* stream);
+/* get_y_coordinate signature.py:84-96: qy[i] = the smaller root of qx^3 + qx + beta, status SP_SQRT_NON_RESIDUE where
+ * the reference raises InvalidPublicKeyError.  qy == NULL: is_valid_stark_key signature.py:204-214 alone, in the
+ * status bytes.  qx is NOT reduced mod p (SP_SQRT_OUT_OF_RANGE); everything else as sp_felt_sqrt_batch. */
+int sp_stark_key_y_batch(const uint64_t* qx, uint64_t* qy, uint8_t* status, size_t n);
+int sp_stark_key_y_batch_dev(const uint64_t* qx, uint64_t* qy, uint8_t* status, size_t n, void* stream);
 
 /* ---- prover-side transforms over GF(p) (build-defined: the reference has no prover) -------------- */
 /* Field and generator: pedersen_params.json:20-21 (FIELD_PRIME, FIELD_GEN = 3).  All pointers are

@@ -35,6 +35,7 @@ void release_stark_state();     // twiddle / coset tables, work buffers (stark.h
 void release_builtin_state();   // work buffers of the builtin segments (builtins.hip)
 void release_ecdsa_state();     // per-signature window tables (ecdsa.hip)
 void release_tree_state();      // persistent sparse trees (merkle.hip)
+void release_keys_state();      // square-root tables (keys.hip)
 
 std::recursive_mutex& global_mu() {
   static std::recursive_mutex mu;
@@ -643,6 +644,7 @@ void sp_shutdown(void) {
   sp::release_stark_state();
   sp::release_builtin_state();
   sp::release_ecdsa_state();
+  sp::release_keys_state();
   sp::release_tree_state();
   sp::release_host_lanes();
   for (int i = 0; i < SP_MAX_CONTEXTS; ++i) {

@@ -303,6 +303,10 @@ struct TimelineScope {  // opens the timeline for the duration of a call (no-op 
   TimelineScope& operator=(const TimelineScope&) = delete;
 };
 int hip_fail(hipError_t e, const char* what);
+// pedersen.hip: the event pair of sp_profile_begin/_end around one launch of another file; call both under the
+// library lock, _end only after _begin returned true
+bool profile_launch_begin(hipStream_t st);
+void profile_launch_end(hipStream_t st, size_t units);
 
 #define SP_HIP(call)                                   \
   do {                                                 \

@@ -19,7 +19,8 @@
 //   * All elements that take part in multiplications are in Montgomery form (x * R mod p).
 //
 // The same header compiles for the host (g++) so the arithmetic can be unit-tested without a GPU;
-// the product library only ever runs it on the device (plus one-off table seeds at sp_init).
+// the product library only ever runs it on the device (plus one-off table seeds at sp_init and the square-root
+// tables of sqrt_tables_build).
 #pragma once
 #include <stdint.h>
 #include <utility>
@@ -279,13 +280,21 @@ SP_HD fe fe_reduce(cols& t) {
   return r;
 }
 
+#if defined(SP_COUNT_FIELD_OPS) && !defined(__HIPCC__)
+extern long sp_field_ops;  // host tests (tests/host/felt_sqrt_shim.cpp): every fe_mul and fe_sqr since the test's reset
+#define SP_COUNT_OP() (++sp_field_ops)
+#else
+#define SP_COUNT_OP() ((void)0)
+#endif
 SP_HD fe fe_mul(const fe& a, const fe& b) {
+  SP_COUNT_OP();
   cols t;
   cols_zero(t);
   cols_mac(t, a, b);
   return fe_reduce(t);
 }
 SP_HD fe fe_sqr(const fe& a) {
+  SP_COUNT_OP();
   cols t;
   cols_zero(t);
   cols_sqr(t, a);
@@ -1225,6 +1234,138 @@ SP_HD fe fn_inv_fermat(const fe& a) {
     }
   }
   return r;
+}
+
+// =============================================================================================
+// Square roots in GF(p) with a fixed number of steps (sqrt_mod, math_utils.py:43-47).
+//
+// p - 1 = 2^192 m with m = 2^59 + 17: the 2-part of the group has order 2^192, the worst case for Tonelli-Shanks
+// (up to 192 * 193 / 2 squarings, and a loop count that depends on the input).  Here, for c != 0:
+//   w = c^((m - 1) / 2) = c^(2^58 + 8),  x = c w,  t = x w = c^m  (so x^2 = c t, and t lies in the subgroup of
+//   order 2^192 generated by g = 3^m);  t = g^e:  c is a residue iff e is even, and then sqrt(c) = x g^(-e / 2).
+// e is found by Pohlig-Hellman in 24 digits of 8 bits, lowest first: T^(2^(184 - 8 k)) lies in the subgroup of order
+// 256, whose 256 members are told apart by a perfect hash of the low 32 bits of their canonical Montgomery value
+// (searched when the tables are built); the digit's table entry s = g^(-d 2^(8 k - 1)) goes into the root, and its
+// square takes the digit out of T.  Digit 0 has no half: it reads g^(-(d >> 1)) for the root and g^(-d) for T, and an
+// odd d is the non-residue answer - such an input runs the same steps to the end.
+// Field operations for every input, residue or not: 59 + 2 (w, x, t) + 2208 squarings (184 + 176 + ... + 0)
+// + 2 (digit 0) + 22 * 3 (digits 1 .. 22) + 1 (digit 23) = 2338.
+constexpr int SQRT_W = 8, SQRT_DIGITS = 192 / SQRT_W, SQRT_HASH_BITS = 12;
+struct alignas(32) sqrt_tables {
+  u256 root[SQRT_DIGITS][1 << SQRT_W];  // [k][d]: g^(-d 2^(8 k - 1)), k >= 1; [0][d]: g^(-(d >> 1)).  Montgomery, canonical
+  u256 strip0[1 << SQRT_W];             // g^(-d)
+  uint8_t digit[1 << SQRT_HASH_BITS];   // slot of h^d -> d, h = g^(2^184); the other slots hold 0 and are never hit
+  uint32_t mult;                        // slot = (low 32 bits * mult) >> (32 - SQRT_HASH_BITS)
+  uint32_t pad[7];
+};
+
+SP_HD uint32_t sqrt_slot(const fe& u, uint32_t mult) {  // u: any N-form of a member of the order-256 subgroup
+  const fe c = fe_canon(u);
+  const uint32_t low = (uint32_t)c.l[0] | ((uint32_t)c.l[1] << LB);
+  return (low * mult) >> (32 - SQRT_HASH_BITS);
+}
+SP_HD fe sqrt_entry(const u256* p) {
+  u256 r;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4* q = reinterpret_cast<const uint4*>(p);  // entries are 32-byte aligned
+  const uint4 a = q[0], b = q[1];
+  r.w[0] = a.x; r.w[1] = a.y; r.w[2] = a.z; r.w[3] = a.w;
+  r.w[4] = b.x; r.w[5] = b.y; r.w[6] = b.z; r.w[7] = b.w;
+#else
+  r = *p;
+#endif
+  return fe_unpack(r);
+}
+// a^(2^58 + 8)
+SP_HD fe fe_pow_2p58_plus8(const fe& a) {
+  fe t = fe_sqr_n(a, 55);
+  t = fe_mul(t, a);
+  return fe_sqr_n(t, 3);
+}
+// c in Montgomery N-form, any value (0 included: every step then computes 0 and the caller answers for it).
+// Returns whether c is a residue; root = one of its two roots (Montgomery N-form) if so.
+SP_HD bool fe_sqrt(const fe& c, const sqrt_tables* tab, fe& root) {
+  const fe w = fe_pow_2p58_plus8(c);
+  fe y = fe_mul(c, w);  // x; collects g^(-e / 2)
+  fe t = fe_mul(y, w);
+  // digit 0
+  uint32_t d = tab->digit[sqrt_slot(fe_sqr_n(t, 192 - SQRT_W), tab->mult)];
+  const bool residue = (d & 1u) == 0;
+  y = fe_mul(y, sqrt_entry(&tab->root[0][d]));
+  t = fe_mul(t, sqrt_entry(&tab->strip0[d]));
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int k = 1; k < SQRT_DIGITS - 1; ++k) {
+    d = tab->digit[sqrt_slot(fe_sqr_n(t, 192 - SQRT_W * (k + 1)), tab->mult)];
+    const fe s = sqrt_entry(&tab->root[k][d]);
+    y = fe_mul(y, s);
+    t = fe_mul(t, fe_sqr(s));
+  }
+  d = tab->digit[sqrt_slot(t, tab->mult)];
+  root = fe_mul(y, sqrt_entry(&tab->root[SQRT_DIGITS - 1][d]));
+  return residue;
+}
+// canonical plain limbs of min(r, p - r) for a Montgomery N-form root
+SP_HD fe fe_smaller_root(const fe& root_m) {
+  const fe r = fe_from_mont(root_m);
+  const fe n = fe_carry(fe_sub(FE_P, r));  // p - r: in (0, p] - p itself only for r = 0, which then keeps r
+  return limbs_geq(n, r) ? r : n;
+}
+
+// Host: the tables from 3 and m.  false when g^(2^191) != -1 or no hash multiplier separates the 256 members of the
+// order-256 subgroup (nothing about them is assumed).
+inline bool sqrt_tables_build(sqrt_tables& tb) {
+  constexpr int ND = 1 << SQRT_W;
+  fe three = FE_ZERO;
+  three.l[0] = 3;
+  three = fe_to_mont(three);
+  const fe g = fe_mul(fe_pow_2p59_plus16(three), three);  // 3^m
+  if (!fe_eq(fe_sqr_n(g, 191), fe_neg(FE_ONE_M))) return false;
+  const fe ginv = fe_inv_fermat(g);
+  auto store = [](u256& dst, const fe& v) { dst = fe_pack(fe_canon(v)); };
+  auto powers = [&](u256* dst, const fe& base, bool halves) {  // dst[d] = base^d (halves: base^(d >> 1))
+    fe acc = FE_ONE_M;
+    for (int d = 0; d < ND; ++d) {
+      store(dst[d], acc);
+      if (!halves || (d & 1)) acc = fe_mul(acc, base);
+    }
+  };
+  powers(tb.strip0, ginv, false);
+  powers(tb.root[0], ginv, true);
+  fe base = fe_sqr_n(ginv, SQRT_W - 1);  // g^(-2^7)
+  for (int k = 1; k < SQRT_DIGITS; ++k) {
+    powers(tb.root[k], base, false);
+    base = fe_sqr_n(base, SQRT_W);
+  }
+  // the subgroup of order 256 and a multiplier that sends its members to 256 different slots
+  const fe h = fe_sqr_n(g, 192 - SQRT_W);
+  uint32_t low[ND];
+  fe acc = FE_ONE_M;
+  for (int d = 0; d < ND; ++d) {
+    const fe c = fe_canon(acc);
+    low[d] = (uint32_t)c.l[0] | ((uint32_t)c.l[1] << LB);
+    acc = fe_mul(acc, h);
+  }
+  uint32_t mult = 0x9e3779b1u;
+  for (int tries = 0; tries < (1 << 22); ++tries, mult = mult * 0x2c9277b5u + 0xac564b06u) {
+    const uint32_t m = mult | 1u;
+    for (int i = 0; i < (1 << SQRT_HASH_BITS); ++i) tb.digit[i] = 0;
+    bool seen[1 << SQRT_HASH_BITS] = {};
+    bool ok = true;
+    for (int d = 0; d < ND && ok; ++d) {
+      const uint32_t slot = (low[d] * m) >> (32 - SQRT_HASH_BITS);
+      ok = !seen[slot];
+      seen[slot] = true;
+      tb.digit[slot] = (uint8_t)d;
+    }
+    if (ok) {
+      tb.mult = m;
+      for (int i = 0; i < 7; ++i) tb.pad[i] = 0;
+      return true;
+    }
+  }
+  return false;
 }
 
 }  // namespace sp

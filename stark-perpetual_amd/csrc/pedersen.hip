@@ -1047,6 +1047,17 @@ struct KernelProfile {
   size_t used = 0;
 };
 static KernelProfile g_prof;
+// the same bracket for a launch of another file (keys.hip); both under the library lock
+bool profile_launch_begin(hipStream_t st) {
+  if (!g_prof.enabled || g_prof.used + 2 > g_prof.ev.size()) return false;
+  (void)hipEventRecord(g_prof.ev[g_prof.used], st);
+  return true;
+}
+void profile_launch_end(hipStream_t st, size_t units) {
+  (void)hipEventRecord(g_prof.ev[g_prof.used + 1], st);
+  g_prof.units.push_back(units);
+  g_prof.used += 2;
+}
 static bool g_split_enabled = getenv("STARKPERP_NO_SPLIT") == nullptr;  // A/B switches
 static bool g_fuse_enabled = getenv("STARKPERP_NO_FUSE") == nullptr;
 static bool g_quad_enabled = getenv("STARKPERP_NO_QUAD") == nullptr;

@@ -149,6 +149,10 @@ _SIGNATURES = {
     "sp_ecdsa_sign_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]),
     "sp_ecdsa_sign_rfc6979_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]),
     "sp_public_key_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "sp_felt_sqrt_batch": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t]),
+    "sp_felt_sqrt_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "sp_stark_key_y_batch": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t]),
+    "sp_stark_key_y_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 

@@ -382,6 +382,46 @@ def public_keys_many(priv_keys):
     return list(zip(unpack_felts(qx, n), unpack_felts(qy, n)))
 
 
+SQRT_OK, SQRT_NON_RESIDUE, SQRT_OUT_OF_RANGE = 0, 1, 2  # include/starkperp.h SP_SQRT_*
+
+
+def _roots(fn, what, values, want_root):
+    """values (Python ints, reduced mod p as the reference's functions reduce them) through one of the two root calls:
+    [root or None] with want_root, else [bool]."""
+    n = len(values)
+    if n == 0:
+        return []
+    lib = _lib.ensure_init()
+    out, st = (new_felts(n) if want_root else None), new_bytes(n)
+    _lib.check(getattr(lib, fn)(pack_felts([v % FIELD_PRIME for v in values]), out, st, n), what)
+    st = bytes(st)[:n]
+    assert SQRT_OUT_OF_RANGE not in st
+    if not want_root:
+        return [s == SQRT_OK for s in st]
+    return [r if s == SQRT_OK else None for r, s in zip(unpack_felts(out, n), st)]
+
+
+def sqrt_mod_many(values):
+    """[sqrt_mod(v, FIELD_PRIME) ...] (math_utils.py:43-47: the smaller root) in one launch (sp_felt_sqrt_batch);
+    None where v is not a quadratic residue (math_utils.py:36-40)."""
+    return _roots("sp_felt_sqrt_batch", "sp_felt_sqrt_batch", values, True)
+
+
+def get_y_coordinates_many(xs, strict=True):
+    """[get_y_coordinate(x) ...] (signature.py:84-96) in one launch (sp_stark_key_y_batch).  A key with no point on the
+    curve raises InvalidPublicKeyError as the scalar function does; with strict=False it gives None in that place."""
+    ys = _roots("sp_stark_key_y_batch", "sp_stark_key_y_batch", xs, True)
+    if strict and any(y is None for y in ys):
+        from .signature import InvalidPublicKeyError
+        raise InvalidPublicKeyError()
+    return ys
+
+
+def is_valid_stark_key_many(xs):
+    """[is_valid_stark_key(x) ...] (signature.py:204-214) in one launch: the Legendre symbol alone, no root."""
+    return _roots("sp_stark_key_y_batch", "sp_stark_key_y_batch", xs, False)
+
+
 def sign_attempt_many(msg_hashes, priv_keys, ks):
     """One pass of the loop body of sign() (signature.py:146-173) per item with explicit nonces.
     Returns (rs, ss, status)."""

@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib
 from .batch import (EC_ORDER, FIELD_PRIME, HASH_OUT_OF_RANGE, HASH_UNHASHABLE, SIGN_BAD_INPUT, SIGN_OK, SIGN_RETRY,
+                    SQRT_NON_RESIDUE, SQRT_OK, SQRT_OUT_OF_RANGE,
                     VERIFY_TRUE, WITNESS_HASH_MISMATCH, WITNESS_LINK_MISMATCH, WITNESS_ROOT_MISMATCH,
                     WITNESS_SIBLING_CHANGED, _raise_hash_status, raise_for_verify_code)
 
@@ -192,6 +193,30 @@ def verify_many(z, r, s, qx, qy=None) -> np.ndarray:
         zi, ri, si = (ints_from_felts(a[i : i + 1])[0] for a in (_felts(z), _felts(r), _felts(s)))
         raise_for_verify_code(int(codes[i]), zi, ri, si)
     return codes == VERIFY_TRUE
+
+
+def _root_call(fn, a, want_root):
+    a = _felts(a)
+    n = a.shape[0]
+    out = np.zeros((n, 4), dtype=np.uint64) if want_root else None
+    st = np.zeros(n, dtype=np.uint8)
+    if n:
+        _lib.check(getattr(_lib.ensure_init(), fn)(_ptr(a), None if out is None else _ptr(out), _ptr(st), n), fn)
+    return out, st
+
+
+def felt_sqrt(a):
+    """uint64[n, 4] felts -> (roots uint64[n, 4], status uint8[n]): sqrt_mod(a, FIELD_PRIME) per row (math_utils.py:43-47,
+    the smaller root; sp_felt_sqrt_batch).  status SQRT_OK / SQRT_NON_RESIDUE / SQRT_OUT_OF_RANGE (a felt that is not
+    below p is passed through and reported, not reduced); the root of a row that is not SQRT_OK stays zero."""
+    return _root_call("sp_felt_sqrt_batch", a, True)
+
+
+def stark_key_y(qx, want_y=True):
+    """x-only keys uint64[n, 4] -> (qy uint64[n, 4] or None, status uint8[n]): get_y_coordinate per row
+    (signature.py:84-96; sp_stark_key_y_batch), SQRT_NON_RESIDUE where the reference raises InvalidPublicKeyError.
+    want_y=False: is_valid_stark_key alone (signature.py:204-214) - no root is extracted."""
+    return _root_call("sp_stark_key_y_batch", qx, want_y)
 
 
 def sign_many(z, d, seeds=None):
