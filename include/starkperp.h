@@ -25,7 +25,8 @@
  *     host-pointer batches that carry no shared state - sp_pedersen_batch, sp_pedersen_chains,
  *     sp_pedersen_chains_ragged, sp_merkle_fold_paths, sp_merkle_verify_paths, sp_merkle_verify_update,
  *     sp_ecdsa_verify_batch (per-signature ladder), sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch,
- *     sp_public_key_batch, sp_felt_sqrt_batch, sp_stark_key_y_batch -
+ *     sp_public_key_batch, sp_felt_sqrt_batch, sp_stark_key_y_batch, sp_ec_mult_batch, sp_ec_lincomb_batch,
+ *     sp_ec_add_batch -
  *     run on one of 16 host lanes (own stream, own staging buffer) and hold the lock only while a
  *     kernel is enqueued: calls from different threads overlap on the device - on the devices, after
  *     sp_init_devices - (a seventeenth concurrent caller waits for a lane).  Keyed verification runs on a lane too and holds the
@@ -91,12 +92,13 @@ int sp_init(int device, int window_bits);
  * window tables - per entry of device_ids; context 0 is the PRIMARY.  What runs where:
  *   - the stateless batches run on ANY context: sp_pedersen_batch, sp_ecdsa_verify_batch (ladder),
  *     sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch, sp_public_key_batch, sp_felt_sqrt_batch,
- *     sp_stark_key_y_batch take the context of the host lane
+ *     sp_stark_key_y_batch, sp_ec_mult_batch, sp_ec_lincomb_batch, sp_ec_add_batch take the context of the host lane
  *     they are handed (lanes go round-robin over the contexts, so concurrent host threads spread over the
  *     devices), and one call of sp_pedersen_batch / sp_ecdsa_verify_batch with 16384 items or more is cut into
  *     one contiguous slice per context, the slices running side by side on host threads of the library; sp_pedersen_batch_dev, sp_pedersen_chains_dev, sp_pedersen_chains_ragged_dev, sp_merkle_fold_paths_dev, sp_merkle_build_dev, sp_merkle_forest_dev,
  *     sp_commit_rows_dev, sp_ecdsa_verify_batch_dev, sp_ecdsa_sign_batch_dev, sp_ecdsa_sign_rfc6979_batch_dev,
- *     sp_public_key_batch_dev, sp_felt_sqrt_batch_dev and sp_stark_key_y_batch_dev run on the device their pointers
+ *     sp_public_key_batch_dev, sp_felt_sqrt_batch_dev, sp_stark_key_y_batch_dev, sp_ec_mult_batch_dev,
+ *     sp_ec_lincomb_batch_dev and sp_ec_add_batch_dev run on the device their pointers
  *     live on (the stream
  *     must belong to that device);
  *   - everything with state - persistent trees, key tables, the prover entry points (twiddle tables, witness
@@ -124,7 +126,8 @@ const char* sp_build_info(void);
 /* Measurement aid: between sp_profile_begin and sp_profile_end every launch of the dominant kernel
  * (ped_accumulate_kernel) is bracketed by HIP events on the stream it is launched on; _end returns
  * the summed kernel time, the number of launches and the number of hashes they processed.  The launches of
- * sp_felt_sqrt_batch* and sp_stark_key_y_batch* are bracketed the same way (units: items). */
+ * sp_felt_sqrt_batch*, sp_stark_key_y_batch* and the three sp_ec_*_batch* calls are bracketed the same way (units:
+ * items). */
 int sp_profile_begin(size_t max_launches);
 int sp_profile_end(double* total_ms, uint64_t* launches, uint64_t* units);
 
@@ -584,6 +587,50 @@ int sp_felt_sqrt_batch_dev(const uint64_t* a, uint64_t* root, uint8_t* status, s
  * status bytes.  qx is NOT reduced mod p (SP_SQRT_OUT_OF_RANGE); everything else as sp_felt_sqrt_batch. */
 int sp_stark_key_y_batch(const uint64_t* qx, uint64_t* qy, uint8_t* status, size_t n);
 int sp_stark_key_y_batch_dev(const uint64_t* qx, uint64_t* qy, uint8_t* status, size_t n, void* stream);
+
+/* ---- point arithmetic on the Stark curve: k P, a EC_GEN + b P, P +- Q ---------------------------------- */
+/* ec_mult / ec_add / ec_double of math_utils.py:59-100 on the Stark curve (alpha = 1, p = FIELD_PRIME), one item per
+ * lane.  Points are affine, x and y in arrays of their own like qx / qy above; scalars are plain 256-bit integers.
+ * per-item status, written for every item, exactly: */
+#define SP_EC_OK 0
+#define SP_EC_INFINITY 1      /* the result is the point at infinity, which has no affine form (the reference's ec_add /
+                                 ec_double assert there) */
+#define SP_EC_OUT_OF_RANGE 2  /* a coordinate is not in [0, p) or a scalar is not in [0, EC_ORDER); nothing is reduced */
+#define SP_EC_NOT_ON_CURVE 3  /* an input point fails y^2 = x^3 + x + beta */
+/* The checks run in that order - the range of every input of the item first, then the curve, then the arithmetic - and
+ * every input point is checked even when its scalar is 0.  rx / ry of an item whose status is not SP_EC_OK are left as
+ * they were.  ry == NULL asks for x alone; status and rx are required; n == 0 is legal.  An output array that overlaps
+ * an input array is SP_ERR_BAD_ARGUMENT (lanes past the end of the batch redo its last item, so in-place would race).
+ * A scalar of 0 is legal: k = 0 gives SP_EC_INFINITY, and in sp_ec_lincomb_batch a zero term drops out.  The result is
+ * the right point or SP_EC_INFINITY for EVERY pair of operands: b P == a EC_GEN (the sum is a doubling), b P ==
+ * -(a EC_GEN) (infinity), P == Q, P == -Q, and the two scalars (30 and EC_ORDER - 30) at which the verifier's ladder
+ * would meet its own operand.
+ *
+ * What these calls are for, in the terms of the signer's section above: PUBLIC data, or the caller's own secrets on the
+ * caller's own device.  k P and b P run the verifier's signed 4-bit window ladder, which reads its per-lane table of
+ * the eight odd multiples of P at addresses that are digits of the scalar, and a EC_GEN gathers EC_GEN table entries
+ * at addresses that are windows of a; the field inversions (two per ladder item) may be variable-time.  a EC_GEN
+ * always walks the gathered EC_GEN table of the verifier: the masked table of STARKPERP_SIGN_MASKED=1 is bypassed
+ * deliberately, since the ladder beside it is address-dependent anyway.
+ * Scratch: the ladder's table is 8 x 36 limbs x 4 bytes = 1152 bytes per lane, per stream, grown by the first call on a
+ * stream that needs more (hipMalloc: a device-wide synchronisation, not capturable into a hipGraph - call once at the
+ * largest n before a capture) and freed by sp_shutdown.  sp_ec_add_batch needs none.  The host calls run on a host lane. */
+/* R = k P */
+int sp_ec_mult_batch(const uint64_t* k, const uint64_t* px, const uint64_t* py, uint64_t* rx, uint64_t* ry,
+                     uint8_t* status, size_t n);
+/* R = a EC_GEN + b P */
+int sp_ec_lincomb_batch(const uint64_t* a, const uint64_t* b, const uint64_t* px, const uint64_t* py, uint64_t* rx,
+                        uint64_t* ry, uint8_t* status, size_t n);
+/* R = P + Q, or P - Q when subtract != 0 */
+int sp_ec_add_batch(const uint64_t* px, const uint64_t* py, const uint64_t* qx, const uint64_t* qy, int subtract,
+                    uint64_t* rx, uint64_t* ry, uint8_t* status, size_t n);
+/* The same on device pointers, on the device they live on: enqueued on `stream`, nothing waited for. */
+int sp_ec_mult_batch_dev(const uint64_t* k, const uint64_t* px, const uint64_t* py, uint64_t* rx, uint64_t* ry,
+                         uint8_t* status, size_t n, void* stream);
+int sp_ec_lincomb_batch_dev(const uint64_t* a, const uint64_t* b, const uint64_t* px, const uint64_t* py,
+                            uint64_t* rx, uint64_t* ry, uint8_t* status, size_t n, void* stream);
+int sp_ec_add_batch_dev(const uint64_t* px, const uint64_t* py, const uint64_t* qx, const uint64_t* qy, int subtract,
+                        uint64_t* rx, uint64_t* ry, uint8_t* status, size_t n, void* stream);
 
 /* ---- prover-side transforms over GF(p) (build-defined: the reference has no prover) -------------- */
 /* Field and generator: pedersen_params.json:20-21 (FIELD_PRIME, FIELD_GEN = 3).  All pointers are

@@ -12,6 +12,7 @@
 
 #include "../../include/starkperp.h"
 #include "curve.hpp"
+#include "u256.hpp"
 
 namespace sp {
 
@@ -308,6 +309,12 @@ int hip_fail(hipError_t e, const char* what);
 bool profile_launch_begin(hipStream_t st);
 void profile_launch_end(hipStream_t st, size_t units);
 
+// whether two caller arrays share a byte (an output of a batch call may not overlap an input)
+inline bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const char *p = (const char*)a, *q = (const char*)b;
+  return p < q + b_bytes && q < p + a_bytes;
+}
+
 #define SP_HIP(call)                                   \
   do {                                                 \
     hipError_t e__ = (call);                           \
@@ -365,25 +372,7 @@ __device__ __forceinline__ aff ld_aff(const aff_packed* e) {
   r.y = fe_unpack(y);
   return r;
 }
-// plain integer a < 2^256 compared with p / N / 2^251 on packed words
-__host__ __device__ __forceinline__ bool u256_lt(const u256& a, const u256& b) {
-  bool lt = false;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    if (a.w[i] != b.w[i]) lt = a.w[i] < b.w[i];  // highest differing word decides
-  }
-  return lt;
-}
-__host__ __device__ __forceinline__ bool u256_is_zero(const u256& a) {
-  uint32_t o = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o |= a.w[i];
-  return o == 0;
-}
-constexpr u256 U256_P = {{1u, 0u, 0u, 0u, 0u, 0u, 0x11u, 0x08000000u}};
-constexpr u256 U256_N = {{0xadc64d2fu, 0x1e66a241u, 0xcae7b232u, 0xb781126du, 0xffffffffu, 0xffffffffu,
-                          0x10u, 0x08000000u}};
-constexpr u256 U256_2P251 = {{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0x08000000u}};
+// u256_lt, u256_is_zero and the bounds U256_P / U256_N / U256_2P251: u256.hpp
 
 // w-bit window number `win` of a 256-bit little-endian integer
 __device__ __forceinline__ uint32_t window_of(const u256& a, int win, int wbits) {

@@ -86,11 +86,6 @@ static int enqueue_keys(bool key, const uint64_t* in, uint64_t* out, uint8_t* st
   return SP_OK;
 }
 
-static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const char *p = (const char*)a, *q = (const char*)b;
-  return p < q + b_bytes && q < p + a_bytes;
-}
-
 static int check_args(const char* who, const uint64_t* in, const uint64_t* out, const uint8_t* status, size_t n) {
   if (!in || !status) { set_error(std::string(who) + ": null pointer"); return SP_ERR_BAD_ARGUMENT; }
   if (out && overlap(in, n * 32, out, n * 32)) {

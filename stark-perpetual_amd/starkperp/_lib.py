@@ -153,6 +153,13 @@ _SIGNATURES = {
     "sp_felt_sqrt_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
     "sp_stark_key_y_batch": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t]),
     "sp_stark_key_y_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "sp_ec_mult_batch": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_size_t]),
+    "sp_ec_mult_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "sp_ec_lincomb_batch": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_size_t]),
+    "sp_ec_lincomb_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]),
+    "sp_ec_add_batch": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_size_t]),
+    "sp_ec_add_batch_dev": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 3
+                            + [ctypes.c_size_t, ctypes.c_void_p]),
 }
 
 

@@ -422,6 +422,58 @@ def is_valid_stark_key_many(xs):
     return _roots("sp_stark_key_y_batch", "sp_stark_key_y_batch", xs, False)
 
 
+EC_OK, EC_INFINITY, EC_OUT_OF_RANGE, EC_NOT_ON_CURVE = 0, 1, 2, 3  # include/starkperp.h SP_EC_*
+
+
+def _ec_call(fn, scalars, point_lists, extra=()):
+    """One of the three point calls on Python ints: [(x, y) or None for infinity].  AssertionError for a scalar outside
+    [0, EC_ORDER), a coordinate outside [0, FIELD_PRIME) or a point off the curve - input the reference's ec_mult /
+    ec_add cannot handle either."""
+    n = len(point_lists[0])
+    for col in scalars:
+        assert len(col) == n
+        for k in col:
+            assert 0 <= k < EC_ORDER
+    for pts in point_lists:
+        assert len(pts) == n
+        for x, y in pts:
+            assert 0 <= x < FIELD_PRIME and 0 <= y < FIELD_PRIME
+    if n == 0:
+        return []
+    lib = _lib.ensure_init()
+    args = [pack_felts(col) for col in scalars]
+    for pts in point_lists:
+        args += [pack_felts([x for x, _ in pts]), pack_felts([y for _, y in pts])]
+    rx, ry, st = new_felts(n), new_felts(n), new_bytes(n)
+    _lib.check(getattr(lib, fn)(*args, *extra, rx, ry, st, n), fn)
+    st = bytes(st)[:n]
+    assert EC_OUT_OF_RANGE not in st
+    assert EC_NOT_ON_CURVE not in st, "point is not on the curve"
+    return [xy if s == EC_OK else None for xy, s in zip(zip(unpack_felts(rx, n), unpack_felts(ry, n)), st)]
+
+
+def ec_mult_many(scalars, points):
+    """[ec_mult(k, P, 1, FIELD_PRIME) ...] (math_utils.py:91-100) in one launch (sp_ec_mult_batch): k in [0, EC_ORDER),
+    P = (x, y) on the Stark curve.  None where the result is the point at infinity (k = 0)."""
+    return _ec_call("sp_ec_mult_batch", [scalars], [points])
+
+
+def ec_lincomb_many(a, b, points):
+    """[a EC_GEN + b P ...] in one launch (sp_ec_lincomb_batch); None where the sum is the point at infinity."""
+    return _ec_call("sp_ec_lincomb_batch", [a, b], [points])
+
+
+def ec_add_many(points1, points2):
+    """[P + Q ...] for every pair, equal and opposite points included (ec_add / ec_double of math_utils.py:59-88 assert
+    there), in one launch (sp_ec_add_batch); None where the sum is the point at infinity."""
+    return _ec_call("sp_ec_add_batch", [], [points1, points2], (0,))
+
+
+def ec_sub_many(points1, points2):
+    """[P - Q ...] in one launch (sp_ec_add_batch with subtract); None where P == Q."""
+    return _ec_call("sp_ec_add_batch", [], [points1, points2], (1,))
+
+
 def sign_attempt_many(msg_hashes, priv_keys, ks):
     """One pass of the loop body of sign() (signature.py:146-173) per item with explicit nonces.
     Returns (rs, ss, status)."""

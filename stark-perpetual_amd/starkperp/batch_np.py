@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .batch import (EC_ORDER, FIELD_PRIME, HASH_OUT_OF_RANGE, HASH_UNHASHABLE, SIGN_BAD_INPUT, SIGN_OK, SIGN_RETRY,
+from .batch import (EC_INFINITY, EC_NOT_ON_CURVE, EC_OK, EC_ORDER, EC_OUT_OF_RANGE, FIELD_PRIME, HASH_OUT_OF_RANGE, HASH_UNHASHABLE, SIGN_BAD_INPUT, SIGN_OK, SIGN_RETRY,
                     SQRT_NON_RESIDUE, SQRT_OK, SQRT_OUT_OF_RANGE,
                     VERIFY_TRUE, WITNESS_HASH_MISMATCH, WITNESS_LINK_MISMATCH, WITNESS_ROOT_MISMATCH,
                     WITNESS_SIBLING_CHANGED, _raise_hash_status, raise_for_verify_code)
@@ -217,6 +217,34 @@ def stark_key_y(qx, want_y=True):
     (signature.py:84-96; sp_stark_key_y_batch), SQRT_NON_RESIDUE where the reference raises InvalidPublicKeyError.
     want_y=False: is_valid_stark_key alone (signature.py:204-214) - no root is extracted."""
     return _root_call("sp_stark_key_y_batch", qx, want_y)
+
+
+def _ec_call(fn, inputs, extra=()):
+    inputs = [_felts(inputs[0])] + [_felts(a, len(inputs[0])) for a in inputs[1:]]
+    n = inputs[0].shape[0]
+    rx, ry = np.zeros((n, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+    st = np.zeros(n, dtype=np.uint8)
+    if n:
+        _lib.check(getattr(_lib.ensure_init(), fn)(*[_ptr(a) for a in inputs], *extra, _ptr(rx), _ptr(ry), _ptr(st), n), fn)
+    return rx, ry, st
+
+
+def ec_mult(k, px, py):
+    """uint64[n, 4] scalars and affine points -> (rx, ry, status): k P per row on the Stark curve (sp_ec_mult_batch;
+    math_utils.py:91-100).  status EC_OK / EC_INFINITY / EC_OUT_OF_RANGE / EC_NOT_ON_CURVE of starkperp.batch; nothing is
+    reduced, and the rows that are not EC_OK stay zero."""
+    return _ec_call("sp_ec_mult_batch", [k, px, py])
+
+
+def ec_lincomb(a, b, px, py):
+    """(rx, ry, status) of a EC_GEN + b P per row (sp_ec_lincomb_batch); rows that are not EC_OK stay zero."""
+    return _ec_call("sp_ec_lincomb_batch", [a, b, px, py])
+
+
+def ec_add(px, py, qx, qy, subtract=False):
+    """(rx, ry, status) of P + Q per row, P - Q with subtract (sp_ec_add_batch): every pair, equal and opposite points
+    included; rows that are not EC_OK stay zero."""
+    return _ec_call("sp_ec_add_batch", [px, py, qx, qy], (1 if subtract else 0,))
 
 
 def sign_many(z, d, seeds=None):
