@@ -643,19 +643,32 @@ int sp_ntt_dev(const uint64_t* in, uint64_t* out, unsigned log_n, int inverse, v
  * pass, above it the padded columns are written out first. */
 int sp_lde_dev(const uint64_t* in, uint64_t* out, unsigned ncols, unsigned log_n, unsigned log_blowup,
                const uint64_t* shift_host, void* stream);
+/* Rules shared by the calls below.
+ *   Empty calls: a witness generator (sp_pedersen_trace_dev, sp_ec_ladder_trace_dev, sp_ecdsa_trace_dev,
+ *     sp_range_check_trace_dev, sp_rc16_trace_dev) given a count of 0 and sp_air_eval_shard_dev given n_points = 0
+ *     return SP_OK: nothing is reserved, launched or written.  A fold shard of count = 0 returns SP_OK too.
+ *   Composition calls (sp_air_eval_dev, _shard_dev, _blocks_dev, sp_air_eval_ec_ladder_dev, sp_air_eval_ecdsa_dev,
+ *     sp_air_eval_range_check_dev, sp_air_eval_rc16_dev): log_n is the trace length and is at least the AIR's period
+ *     - 9 .. 30 for the Pedersen-step AIR (all three of its calls; the shard calls take the GLOBAL log_n), 8 .. 30
+ *     for the EC ladder, 10 .. 30 for ECDSA, 7 .. 30 for the range check, 3 .. 24 for rc16 - and the shift is
+ *     neither 0 nor a felt with shift^n * w_4^k = 1 for some k (that is shift^(4n) = 1: 1, p - 1, any power of
+ *     w_{4n}): x^n - 1 vanishes on such a coset and the column does not exist.  Either violation is
+ *     SP_ERR_BAD_ARGUMENT before anything is launched; sp_last_error() names the call and says "log_n" or "shift".
+ *   Folds (sp_fri_fold_dev, _shard_dev, _blocks_dev): a shift of 0 is SP_ERR_BAD_ARGUMENT (the fold divides by 2 x). */
 /* Execution trace of the Pedersen-step AIR: 512 rows per hash, columns s, px, py, lambda
  * (cols = 4 columns of 512 * n_hashes felts).  Step relation: signature.py:305-317 with the chord
  * rule of math_utils.py:59-68. */
 int sp_pedersen_trace_dev(const uint64_t* x, const uint64_t* y, size_t n_hashes, uint64_t* cols,
                           void* stream);
 /* Composition column sum_k alpha_k C_k(x) / (x^n - 1) on the blowup-4 coset.  trace_lde: 4 columns of
- * 4 * 2^log_n felts; periodic_lde: 6 tables of 2048 felts; alphas_host: 11 felts. */
+ * 4 * 2^log_n felts; periodic_lde: 6 tables of 2048 felts; alphas_host: 11 felts.  9 <= log_n <= 30. */
 int sp_air_eval_dev(const uint64_t* trace_lde, const uint64_t* periodic_lde, unsigned log_n,
                     const uint64_t* alphas_host, const uint64_t* shift_host, uint64_t* out, void* stream);
 /* Row shard of the same column for one rank of a multi-GPU job (SURVEY 8(e) "AIR eval": LDE-row shards
  * with a halo of one trace row): n_points LDE points from global index row0 (a multiple of 4); the four
  * columns are col_stride felts apart and hold n_points + 4 rows, the last four received from the owner of
- * the following rows.  log_n is the global trace length. */
+ * the following rows (the owner of the last rows receives rows 0 .. 3).  log_n is the global trace length.
+ * SP_ERR_BAD_ARGUMENT: row0 not a multiple of 4, col_stride < n_points + 4, row0 + n_points > 4 * 2^log_n. */
 int sp_air_eval_shard_dev(const uint64_t* trace_lde, size_t col_stride, size_t n_points, size_t row0,
                           const uint64_t* periodic_lde, unsigned log_n, const uint64_t* alphas_host,
                           const uint64_t* shift_host, uint64_t* out, void* stream);
@@ -687,7 +700,12 @@ int sp_air_eval_range_check_dev(const uint64_t* trace_lde, const uint64_t* perio
  * sorts a into s); sp_rc16_product_dev writes p (n felts); sp_air_eval_rc16_dev the rc16 part of the
  * composition column (cols: a, acc, s of 4 * 2^log_n felts each; periodic_lde: 2 tables of 32 felts;
  * alphas_host: 8 felts) - transition, all-but-last-row and boundary constraints.  sp_felt_add_dev sums the
- * composition parts of the segments of a combined trace. */
+ * composition parts of the segments of a combined trace.
+ * sp_rc16_product_dev PRECONDITION, not checked: z differs from every s_j.  The denominators z - s_j are inverted
+ * in groups of 16 consecutive cells with one inversion per group; a z that equals some s_j zeroes that group's
+ * product, so all 16 quotients of the group come out 0 and every p_i from the group's first cell to the end of the
+ * column is 0 - with SP_OK.  z is a Fiat-Shamir challenge over the whole field and s_j < 2^16, so a prover never
+ * meets this; a caller that picks z by hand must avoid the values of s. */
 int sp_rc16_trace_dev(const uint64_t* values, size_t n_values, uint64_t* cols, void* stream);
 int sp_rc16_product_dev(const uint64_t* a, const uint64_t* s, size_t n, const uint64_t* z_host, uint64_t* p,
                         void* stream);

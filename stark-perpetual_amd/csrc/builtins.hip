@@ -178,6 +178,9 @@ void release_builtin_state() {
   g_builtin_work.clear();
 }
 
+// stark.hip: 1 / (x^n - 1) at the four residues i mod 4 of the coset, or SP_ERR_BAD_ARGUMENT for a shift it vanishes on
+int air_zinv(const char* who, const uint64_t* shift_host, unsigned log_n, bool times_r2, fe zinv[4]);
+
 static fe h_pow(fe base_m, uint64_t e) {
   fe r = FE_ONE_M;
   for (int i = 63; i >= 0; --i) {
@@ -264,13 +267,9 @@ int sp_air_eval_rc16_dev(const uint64_t* cols, const uint64_t* p, const uint64_t
   Rc16AirParams prm;
   for (int k = 0; k < 8; ++k) prm.alpha[k] = host_felt_m(alphas_host + 4 * k);
   const fe shift_m = host_felt_m(shift_host);
-  fe sn = shift_m;
-  for (unsigned i = 0; i < log_n; ++i) sn = fe_sqr(sn);
-  const fe w4 = h_root(2);
-  fe wk = FE_ONE_M;
-  for (int k = 0; k < 4; ++k) {
-    prm.zinv[k] = fe_inv(fe_carry(fe_sub(fe_mul(sn, wk), FE_ONE_M)));
-    wk = fe_mul(wk, w4);
+  {  // this composition keeps its Montgomery factors itself: no R^2 on zinv
+    const int rc = air_zinv("sp_air_eval_rc16_dev", shift_host, log_n, false, prm.zinv);
+    if (rc != SP_OK) return rc;
   }
   prm.z = host_felt_m(z_host);
   prm.rc_min = fe_to_mont(fe{{(int32_t)rc_min, 0, 0, 0, 0, 0, 0, 0, 0}});

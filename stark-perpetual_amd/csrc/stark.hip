@@ -1094,6 +1094,31 @@ static fe h_root_of_unity(int log_n) {
 }
 static fe h_inv(const fe& a) { return fe_inv(a); }
 
+// 1 / (x^n - 1) at the four residues i mod 4 of the blowup-4 coset, where x^n = shift^n * w_4^(i mod 4): Montgomery form,
+// times R^2 when `times_r2` (the compositions whose selectors leave one 1/R; the rc16 one does not).  Fails - with the
+// message set - when shift is 0 or one of the four denominators is 0, i.e. shift^(4n) = 1: the coset then meets the trace
+// domain, where the composition does not exist (and the coset points of the rc16 boundary constraints hit 1 and g^-1).
+int air_zinv(const char* who, const uint64_t* shift_host, unsigned log_n, bool times_r2, fe zinv[4]) {
+  u256 sh;
+  std::memcpy(sh.w, shift_host, 32);
+  fe sn = fe_to_mont(fe_unpack(sh));
+  bool bad = fe_is_zero(sn);
+  for (unsigned i = 0; i < log_n; ++i) sn = fe_sqr(sn);
+  const fe w4 = h_root_of_unity(2);
+  fe wk = FE_ONE_M;
+  for (int k = 0; k < 4 && !bad; ++k) {
+    bad = fe_eq(fe_mul(sn, wk), FE_ONE_M);
+    const fe inv = fe_inv(fe_carry(fe_sub(fe_mul(sn, wk), FE_ONE_M)));
+    zinv[k] = times_r2 ? fe_mul(inv, FE_R2) : inv;
+    wk = fe_mul(wk, w4);
+  }
+  if (bad) {
+    set_error(std::string(who) + ": bad shift (0, or shift^n * w4^k = 1 for some k: x^n - 1 vanishes on the coset)");
+    return SP_ERR_BAD_ARGUMENT;
+  }
+  return SP_OK;
+}
+
 static int build_powers(DeviceBuffer& buf, size_t count, fe base_m, fe factor_m, hipStream_t st) {
   SP_HIP(buf.reserve(count * 32 + 64));
   int nbits = 0;
@@ -1344,6 +1369,7 @@ int sp_lde_dev(const uint64_t* in, uint64_t* out, unsigned ncols, unsigned log_n
 int sp_pedersen_trace_dev(const uint64_t* x, const uint64_t* y, size_t n_hashes, uint64_t* cols,
                           void* stream) {
   SP_REQUIRE_READY();
+  if (n_hashes == 0) return SP_OK;
   ctx_lock lk(ctx().mu);
   hipStream_t st = (hipStream_t)stream;
   if (!g_tab.bits_ready) {
@@ -1393,8 +1419,15 @@ int sp_pedersen_trace_dev(const uint64_t* x, const uint64_t* y, size_t n_hashes,
   return SP_OK;
 }
 
-static int air_eval_launch(const uint64_t* trace_lde, size_t col_stride, size_t n_points, size_t row0, int wrap,
-                           const uint64_t* periodic_lde, unsigned log_n, const uint64_t* alphas_host,
+// the trace lengths the three entry points of the Pedersen-step composition admit
+static bool air_log_n_ok(const char* who, unsigned log_n) {
+  if (log_n >= 9 && log_n <= 30) return true;
+  set_error(std::string(who) + ": log_n out of range (one hash is 512 rows)");
+  return false;
+}
+
+static int air_eval_launch(const char* who, const uint64_t* trace_lde, size_t col_stride, size_t n_points, size_t row0,
+                           int wrap, const uint64_t* periodic_lde, unsigned log_n, const uint64_t* alphas_host,
                            const uint64_t* shift_host, uint64_t* out, void* stream, int log_block = -1,
                            size_t blk_mul = 1, size_t blk_add = 0) {
   AirParams prm;
@@ -1403,18 +1436,8 @@ static int air_eval_launch(const uint64_t* trace_lde, size_t col_stride, size_t 
     std::memcpy(a.w, alphas_host + 4 * k, 32);
     prm.alpha[k] = fe_to_mont(fe_unpack(a));
   }
-  u256 sh;
-  std::memcpy(sh.w, shift_host, 32);
-  const fe shift_m = fe_to_mont(fe_unpack(sh));
-  // x^n on the coset = shift^n * w_4^(i mod 4)
-  fe sn = shift_m;
-  for (unsigned i = 0; i < log_n; ++i) sn = fe_sqr(sn);
-  const fe w4 = h_root_of_unity(2);
-  fe wk = FE_ONE_M;
-  for (int k = 0; k < 4; ++k) {
-    prm.zinv[k] = fe_mul(fe_inv(fe_carry(fe_sub(fe_mul(sn, wk), FE_ONE_M))), FE_R2);  // zinv * R^2
-    wk = fe_mul(wk, w4);
-  }
+  const int rc = air_zinv(who, shift_host, log_n, true, prm.zinv);
+  if (rc != SP_OK) return rc;
   prm.shift_x = fe_unpack(PT_SHIFT_X);
   prm.shift_y = fe_unpack(PT_SHIFT_Y);
   hipLaunchKernelGGL(air_eval_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -1426,9 +1449,11 @@ static int air_eval_launch(const uint64_t* trace_lde, size_t col_stride, size_t 
 int sp_air_eval_dev(const uint64_t* trace_lde, const uint64_t* periodic_lde, unsigned log_n,
                     const uint64_t* alphas_host, const uint64_t* shift_host, uint64_t* out, void* stream) {
   SP_REQUIRE_READY();
+  if (!air_log_n_ok("sp_air_eval_dev", log_n)) return SP_ERR_BAD_ARGUMENT;
   ctx_lock lk(ctx().mu);
   const size_t M = (size_t)4 << log_n;
-  return air_eval_launch(trace_lde, M, M, 0, 1, periodic_lde, log_n, alphas_host, shift_host, out, stream);
+  return air_eval_launch("sp_air_eval_dev", trace_lde, M, M, 0, 1, periodic_lde, log_n, alphas_host, shift_host, out,
+                         stream);
 }
 
 // Row shard of the composition column (multi-GPU): n_points LDE points starting at global index row0 (a
@@ -1438,18 +1463,22 @@ int sp_air_eval_shard_dev(const uint64_t* trace_lde, size_t col_stride, size_t n
                           const uint64_t* periodic_lde, unsigned log_n, const uint64_t* alphas_host,
                           const uint64_t* shift_host, uint64_t* out, void* stream) {
   SP_REQUIRE_READY();
-  if ((row0 & 3) != 0 || col_stride < n_points + 4 || row0 + n_points > ((size_t)4 << log_n)) {
+  if (!air_log_n_ok("sp_air_eval_shard_dev", log_n)) return SP_ERR_BAD_ARGUMENT;
+  const size_t M = (size_t)4 << log_n;
+  if ((row0 & 3) != 0 || n_points > M || row0 > M - n_points || col_stride < n_points + 4) {
     set_error("bad composition shard");
     return SP_ERR_BAD_ARGUMENT;
   }
+  if (n_points == 0) return SP_OK;  // nothing to evaluate: no launch (a grid of zero blocks is a launch error)
   ctx_lock lk(ctx().mu);
-  return air_eval_launch(trace_lde, col_stride, n_points, row0, 0, periodic_lde, log_n, alphas_host, shift_host, out,
-                         stream);
+  return air_eval_launch("sp_air_eval_shard_dev", trace_lde, col_stride, n_points, row0, 0, periodic_lde, log_n,
+                         alphas_host, shift_host, out, stream);
 }
 
 int sp_ec_ladder_trace_dev(const uint64_t* m, const uint64_t* qx, const uint64_t* qy, size_t n_ladders,
                            uint64_t* cols, void* stream) {
   SP_REQUIRE_READY();
+  if (n_ladders == 0) return SP_OK;
   ctx_lock lk(ctx().mu);
   aff_packed shift;
   shift.x = fe_pack(fe_canon(fe_to_mont(fe_unpack(PT_SHIFT_X))));
@@ -1467,6 +1496,10 @@ int sp_air_eval_ec_ladder_dev(const uint64_t* trace_lde, const uint64_t* periodi
                               void* stream) {
   SP_REQUIRE_READY();
   ctx_lock lk(ctx().mu);
+  if (log_n < 8 || log_n > 30) {
+    set_error("sp_air_eval_ec_ladder_dev: log_n out of range (one ladder is 256 rows)");
+    return SP_ERR_BAD_ARGUMENT;
+  }
   const size_t n = (size_t)1 << log_n, M = 4 * n;
   EcAirParams prm;
   for (int k = 0; k < 12; ++k) {
@@ -1474,16 +1507,8 @@ int sp_air_eval_ec_ladder_dev(const uint64_t* trace_lde, const uint64_t* periodi
     std::memcpy(a.w, alphas_host + 4 * k, 32);
     prm.alpha[k] = fe_to_mont(fe_unpack(a));
   }
-  u256 sh;
-  std::memcpy(sh.w, shift_host, 32);
-  fe sn = fe_to_mont(fe_unpack(sh));
-  for (unsigned i = 0; i < log_n; ++i) sn = fe_sqr(sn);
-  const fe w4 = h_root_of_unity(2);
-  fe wk = FE_ONE_M;
-  for (int k = 0; k < 4; ++k) {
-    prm.zinv[k] = fe_mul(fe_inv(fe_carry(fe_sub(fe_mul(sn, wk), FE_ONE_M))), FE_R2);  // zinv * R^2
-    wk = fe_mul(wk, w4);
-  }
+  const int rc = air_zinv("sp_air_eval_ec_ladder_dev", shift_host, log_n, true, prm.zinv);
+  if (rc != SP_OK) return rc;
   prm.shift_x = fe_unpack(PT_SHIFT_X);
   prm.shift_y = fe_unpack(PT_SHIFT_Y);
   hipLaunchKernelGGL(air_eval_ec_ladder_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0,
@@ -1518,16 +1543,8 @@ int sp_air_eval_range_check_dev(const uint64_t* trace_lde, const uint64_t* perio
     std::memcpy(a.w, alphas_host + 4 * k, 32);
     prm.alpha[k] = fe_to_mont(fe_unpack(a));
   }
-  u256 sh;
-  std::memcpy(sh.w, shift_host, 32);
-  fe sn = fe_to_mont(fe_unpack(sh));
-  for (unsigned i = 0; i < log_n; ++i) sn = fe_sqr(sn);
-  const fe w4 = h_root_of_unity(2);
-  fe wk = FE_ONE_M;
-  for (int k = 0; k < 4; ++k) {
-    prm.zinv[k] = fe_mul(fe_inv(fe_carry(fe_sub(fe_mul(sn, wk), FE_ONE_M))), FE_R2);  // zinv * R^2
-    wk = fe_mul(wk, w4);
-  }
+  const int rc = air_zinv("sp_air_eval_range_check_dev", shift_host, log_n, true, prm.zinv);
+  if (rc != SP_OK) return rc;
   hipLaunchKernelGGL(air_eval_range_check_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, trace_lde, periodic_lde, M, prm, out);
   SP_HIP(hipGetLastError());
@@ -1537,6 +1554,7 @@ int sp_air_eval_range_check_dev(const uint64_t* trace_lde, const uint64_t* perio
 int sp_ecdsa_trace_dev(const uint64_t* z, const uint64_t* r, const uint64_t* w, const uint64_t* qx,
                        const uint64_t* qy, size_t n_sigs, uint64_t* cols, void* stream) {
   SP_REQUIRE_READY();
+  if (n_sigs == 0) return SP_OK;
   ctx_lock lk(ctx().mu);
   aff_packed shift, gen;
   shift.x = fe_pack(fe_canon(fe_to_mont(fe_unpack(PT_SHIFT_X))));
@@ -1555,6 +1573,10 @@ int sp_air_eval_ecdsa_dev(const uint64_t* trace_lde, const uint64_t* periodic_ld
                           const uint64_t* alphas_host, const uint64_t* shift_host, uint64_t* out, void* stream) {
   SP_REQUIRE_READY();
   ctx_lock lk(ctx().mu);
+  if (log_n < 10 || log_n > 30) {
+    set_error("sp_air_eval_ecdsa_dev: log_n out of range (one verification is 1024 rows)");
+    return SP_ERR_BAD_ARGUMENT;
+  }
   const size_t n = (size_t)1 << log_n, M = 4 * n;
   EcdsaAirParams prm;
   for (int k = 0; k < 26; ++k) {
@@ -1562,16 +1584,8 @@ int sp_air_eval_ecdsa_dev(const uint64_t* trace_lde, const uint64_t* periodic_ld
     std::memcpy(a.w, alphas_host + 4 * k, 32);
     prm.alpha[k] = fe_to_mont(fe_unpack(a));
   }
-  u256 sh;
-  std::memcpy(sh.w, shift_host, 32);
-  fe sn = fe_to_mont(fe_unpack(sh));
-  for (unsigned i = 0; i < log_n; ++i) sn = fe_sqr(sn);
-  const fe w4 = h_root_of_unity(2);
-  fe wk = FE_ONE_M;
-  for (int k = 0; k < 4; ++k) {
-    prm.zinv[k] = fe_mul(fe_inv(fe_carry(fe_sub(fe_mul(sn, wk), FE_ONE_M))), FE_R2);  // zinv * R^2
-    wk = fe_mul(wk, w4);
-  }
+  const int rc = air_zinv("sp_air_eval_ecdsa_dev", shift_host, log_n, true, prm.zinv);
+  if (rc != SP_OK) return rc;
   prm.sx = fe_unpack(PT_SHIFT_X);
   prm.sy = fe_unpack(PT_SHIFT_Y);
   prm.gx = fe_unpack(PT_GEN_X);
@@ -1598,16 +1612,18 @@ static int fri_fold_launch(const uint64_t* fa, const uint64_t* fb, uint64_t* out
                            size_t count, const uint64_t* beta_host, const uint64_t* shift_host, void* stream,
                            int log_block = -1, size_t blk_mul = 1, size_t blk_add = 0) {
   hipStream_t st = (hipStream_t)stream;
+  u256 b, s;
+  std::memcpy(b.w, beta_host, 32);
+  std::memcpy(s.w, shift_host, 32);
+  const fe shift_m = fe_to_mont(fe_unpack(s));
+  if (fe_is_zero(shift_m)) { set_error("fold: bad shift (0: the fold divides by 2 x)"); return SP_ERR_BAD_ARGUMENT; }
   const uint64_t* tw;
   int log_tw = 0;
   int rc = fri_twiddles((int)log_m, &tw, &log_tw, st);
   if (rc != SP_OK) return rc;
-  u256 b, s;
-  std::memcpy(b.w, beta_host, 32);
-  std::memcpy(s.w, shift_host, 32);
   const fe two = fe_to_mont(fe{{2, 0, 0, 0, 0, 0, 0, 0, 0}});
   const fe c1 = fe_inv(two);
-  const fe c2 = fe_mul(fe_to_mont(fe_unpack(b)), fe_inv(fe_mul(two, fe_to_mont(fe_unpack(s)))));
+  const fe c2 = fe_mul(fe_to_mont(fe_unpack(b)), fe_inv(fe_mul(two, shift_m)));
   if (count == 0) return SP_OK;
   hipLaunchKernelGGL(fri_fold_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, fa, fb, out,
                      (int)log_m, i0, count, tw, log_tw, c1, c2, log_block, blk_mul, blk_add);
@@ -1659,6 +1675,7 @@ int sp_air_eval_blocks_dev(const uint64_t* trace_lde, size_t col_stride, size_t 
                            unsigned world, unsigned rank, const uint64_t* periodic_lde, unsigned log_n,
                            const uint64_t* alphas_host, const uint64_t* shift_host, uint64_t* out, void* stream) {
   SP_REQUIRE_READY();
+  if (!air_log_n_ok("sp_air_eval_blocks_dev", log_n)) return SP_ERR_BAD_ARGUMENT;
   const size_t B = (size_t)1 << log_block;
   if (log_block < 2 || log_block > 26 || world == 0 || rank >= world || col_stride < n_blocks * (B + 4) ||
       n_blocks * B * world != ((size_t)4 << log_n)) {
@@ -1666,8 +1683,8 @@ int sp_air_eval_blocks_dev(const uint64_t* trace_lde, size_t col_stride, size_t 
     return SP_ERR_BAD_ARGUMENT;
   }
   ctx_lock lk(ctx().mu);
-  return air_eval_launch(trace_lde, col_stride, n_blocks * B, 0, 0, periodic_lde, log_n, alphas_host, shift_host, out,
-                         stream, (int)log_block, world, rank);
+  return air_eval_launch("sp_air_eval_blocks_dev", trace_lde, col_stride, n_blocks * B, 0, 0, periodic_lde, log_n,
+                         alphas_host, shift_host, out, stream, (int)log_block, world, rank);
 }
 
 // The two halves of sp_lde_dev as separate calls, so that the coset transforms of one column share ONE
