@@ -328,6 +328,32 @@ __device__ __forceinline__ xyzz split_accumulate(const uint64_t* fx, const uint6
   return acc;
 }
 
+// The fused epilogue of a lane-split sum (ped_accumulate_split_kernel<LOG_L, true>, ped_tail_kernel): the plain affine
+// x = X / ZZ on every lane; *st becomes SP_HASH_UNHASHABLE when ZZ = 0.  Every lane of the wave must be active.
+template <int LOG_L>
+__device__ __forceinline__ u256 split_fused_x(const xyzz& acc, uint8_t* st) {
+  // EVERY lane takes part in the inversion (an inversion under a 1-lane-in-8 execution mask takes 4x as
+  // long as the same code with all lanes active, tools/ubench/inv_lanes.hip), and a DPP quad always
+  // shares ONE quad-split divsteps run: its lanes hold one sum (L >= 4), two (L = 2) or four different
+  // ones (L = 1), multiplied together first and separated afterwards (quad.hpp fe_inv_shared_quad).
+  fe zz = acc.ZZ;
+  // ZZ = 0: an exceptional addition happened (signature.py:313 territory).  Lanes that SHARE an inversion with
+  // other sums (L < 4) must find that out first - a zero would spoil the product of the quad; where the quad
+  // holds one sum the test costs nothing: the inversion answers 0 for a multiple of p, and only for one.
+  if constexpr (LOG_L < 2) {
+    if (fe_is_zero(zz)) {
+      zz = FE_ONE_M;
+      *st = SP_HASH_UNHASHABLE;
+    }
+  }
+  // the inverse without its Montgomery factor: X R x ZZ^-1 is already the plain x (no fe_from_mont pass)
+  const fe zinv = fe_inv_shared_quad<(LOG_L >= 2 ? 0 : 2 - LOG_L), true>(zz, (int)(threadIdx.x & 3));
+  if constexpr (LOG_L >= 2) {
+    if (limbs_is_zero(zinv)) *st = SP_HASH_UNHASHABLE;
+  }
+  return fe_pack(fe_canon(fe_mul(acc.X, zinv)));
+}
+
 // FUSED: lane 0 of each group also inverts ZZ and writes the affine x itself - no scratch planes and
 // no second launch.  Used only while the whole level fits one wave per SIMD (the inversion then costs
 // latency, not throughput): it saves the launch gap and the plane round trip of the small levels.
@@ -350,28 +376,7 @@ ped_accumulate_split_kernel(const uint64_t* __restrict__ x, const uint64_t* __re
   const xyzz acc = split_accumulate<LOG_L>(fx, fy, sub, ped, w0, log2e, nwin);
   uint8_t st = SP_HASH_OK;
   u256 xa_plain;
-  if (FUSED) {
-    // EVERY lane takes part in the inversion (an inversion under a 1-lane-in-8 execution mask takes 4x as
-    // long as the same code with all lanes active, tools/ubench/inv_lanes.hip), and a DPP quad always
-    // shares ONE quad-split divsteps run: its lanes hold one sum (L >= 4), two (L = 2) or four different
-    // ones (L = 1), multiplied together first and separated afterwards (quad.hpp fe_inv_shared_quad).
-    fe zz = acc.ZZ;
-    // ZZ = 0: an exceptional addition happened (signature.py:313 territory).  Lanes that SHARE an inversion with
-    // other sums (L < 4) must find that out first - a zero would spoil the product of the quad; where the quad
-    // holds one sum the test costs nothing: the inversion answers 0 for a multiple of p, and only for one.
-    if constexpr (LOG_L < 2) {
-      if (fe_is_zero(zz)) {
-        zz = FE_ONE_M;
-        st = SP_HASH_UNHASHABLE;
-      }
-    }
-    // the inverse without its Montgomery factor: X R x ZZ^-1 is already the plain x (no fe_from_mont pass)
-    const fe zinv = fe_inv_shared_quad<(LOG_L >= 2 ? 0 : 2 - LOG_L), true>(zz, (int)(threadIdx.x & 3));
-    if constexpr (LOG_L >= 2) {
-      if (limbs_is_zero(zinv)) st = SP_HASH_UNHASHABLE;
-    }
-    xa_plain = fe_pack(fe_canon(fe_mul(acc.X, zinv)));
-  }
+  if (FUSED) xa_plain = split_fused_x<LOG_L>(acc, &st);
   if (!active || sub != 0) return;
   if (!u256_lt(ld_u256(fx), U256_P) || !u256_lt(ld_u256(fy), U256_P)) st = SP_HASH_OUT_OF_RANGE;
   if (FUSED) {
@@ -820,6 +825,80 @@ ped_top_kernel(uint64_t* __restrict__ cur, size_t n_in, int n_levels, const aff_
   }
 }
 
+// One hash on the 2^S lanes that share it, by the body of its size class: the fused lane-split sum (S = 0..2:
+// ped_accumulate_split_kernel<S, true>), then the quad kernels' (S = 3..5: ped_quad_kernel<S - 2>).  The plain affine
+// x on every lane of the group; *st becomes SP_HASH_UNHASHABLE after an exceptional addition.
+template <int S>
+__device__ __forceinline__ u256 tail_hash(const uint64_t* fx, const uint64_t* fy, int lane, const aff_packed* __restrict__ ped,
+                                          int w0, int log2e, int nwin, uint8_t* st) {
+  if constexpr (S < 3) {
+    return split_fused_x<S>(split_accumulate<S>(fx, fy, lane, ped, w0, log2e, nwin), st);
+  } else {
+    bool unhashable;
+    const u256 xa = quad_hash<S - 2, false>(fx, fy, 0, nullptr, 0, 0, ped, w0, log2e, nwin, lane, &unhashable);
+    if (unhashable) *st = SP_HASH_UNHASHABLE;
+    return xa;
+  }
+}
+
+// ped_top_kernel from the first level that fits one wave per SIMD: every such level of a dense forest halves the
+// hashes and doubles the lanes per hash (1, 2, 4 lanes: the lane-split body; 8, 16, 32: the quad body), so the 256
+// threads of a block stay busy on 2 (256 >> s0) consecutive nodes of the entry level - s0 = log2 of its lanes per
+// hash - all the way down to ONE node, 9 - s0 levels later: 256 >> s hashes of 2^s lanes at lane class s = s0, s0 + 1,
+// ..., 5, then 4, 2, 1 hashes that 2, 4, 8 groups of 32 lanes each compute alike (ped_top_kernel's `dup` idiom).  The
+// lane plan, the chain and the results of every level are those of its own launch (enqueue_pedersen_impl); the launch
+// boundaries and the HBM round trips between them go.  Node values pass through two LDS slot arrays, written and read
+// alternately (one barrier per level), and go to their place in the level-major buffer.  The level loop is rolled and
+// the classes are cases of one switch: a level runs the code of one class only, which fits the instruction cache as
+// it does in that class's own kernel.  n_in is a multiple of the block's chunk (the host's dispatch rule).
+__global__ void __launch_bounds__(256)
+ped_tail_kernel(uint64_t* __restrict__ cur, size_t n_in, int s0, int n_levels, const aff_packed* __restrict__ ped, int w0,
+                int log2e, int nwin_plan, unsigned* __restrict__ flag) {
+  __shared__ uint64_t slot[2][256][4];
+  const size_t b = blockIdx.x;
+  const int tid = (int)threadIdx.x;
+  uint64_t* out = cur + 4 * n_in;  // level j + 1
+  size_t n_out = n_in >> 1;
+#pragma unroll 1
+  for (int t = 0; t < n_levels; ++t) {
+    const int s = s0 + t;           // 2^s threads per hash at this level (s <= 8) ...
+    const int cls = s < 5 ? s : 5;  // ... in groups of 2^cls lanes; every group of a hash computes it
+    const int cnt = 256 >> s;       // hashes of this block at this level
+    const int i = tid >> s, lane = tid & ((1 << cls) - 1);
+    const bool writer = (tid & ((1 << s) - 1)) == 0;
+    const uint64_t *fx, *fy;
+    if (t == 0) {
+      fx = cur + 4 * (2 * (size_t)cnt * b + 2 * (size_t)i);
+      fy = fx + 4;
+    } else {
+      fx = slot[(t - 1) & 1][2 * i];
+      fy = slot[(t - 1) & 1][2 * i + 1];
+    }
+    uint8_t st = SP_HASH_OK;
+    u256 xa;
+    switch (cls) {
+      case 0: xa = tail_hash<0>(fx, fy, lane, ped, w0, log2e, nwin_plan, &st); break;
+      case 1: xa = tail_hash<1>(fx, fy, lane, ped, w0, log2e, nwin_plan, &st); break;
+      case 2: xa = tail_hash<2>(fx, fy, lane, ped, w0, log2e, nwin_plan, &st); break;
+      case 3: xa = tail_hash<3>(fx, fy, lane, ped, w0, log2e, nwin_plan, &st); break;
+      case 4: xa = tail_hash<4>(fx, fy, lane, ped, w0, log2e, nwin_plan, &st); break;
+      default: xa = tail_hash<5>(fx, fy, lane, ped, w0, log2e, nwin_plan, &st); break;
+    }
+    // only the first level can see a caller's value (the leaves); above it the operands are hash outputs
+    if (t == 0 && writer && (!u256_lt(ld_u256(fx), U256_P) || !u256_lt(ld_u256(fy), U256_P))) st = SP_HASH_OUT_OF_RANGE;
+    if (writer) {
+      uint32_t* sl = reinterpret_cast<uint32_t*>(slot[t & 1][i]);
+#pragma unroll
+      for (int w = 0; w < 8; ++w) sl[w] = xa.w[w];
+      st_u256(out + 4 * ((size_t)cnt * b + (size_t)i), xa);
+      if (st != SP_HASH_OK && flag) atomicOr(flag, (unsigned)st);
+    }
+    __syncthreads();
+    out += 4 * n_out;
+    n_out >>= 1;
+  }
+}
+
 // Kernel B: thread t owns elements t, t+T, t+2T, ...; one inversion per thread (Montgomery's trick).
 // Launched with at most one wave per SIMD when it can be (finish_threads), so nothing hides a load:
 // both passes are software-pipelined by hand (the operands of element j +- 1 are requested before
@@ -1214,6 +1293,29 @@ int enqueue_partial_points(const uint64_t* felts, int count, aff_packed* out, hi
   return SP_OK;
 }
 
+// log2 of the lanes per hash of the lane-split kernel for a launch of n hashes (enqueue_pedersen_impl): as many as
+// still fit one wave per SIMD, every lane with at least two windows.
+static int split_log_l(size_t n, int nwin) {
+  int log_l = 0;
+  if (g_split_enabled) {
+    if (n * 8 <= g_split_lanes) log_l = 3;
+    else if (n * 4 <= g_split_lanes) log_l = 2;
+    else if (n * 2 <= g_split_lanes) log_l = 1;
+    while (log_l > 0 && nwin < (2 << log_l)) --log_l;
+  }
+  return log_l;
+}
+// The lane class s (2^s lanes per hash) of ped_tail_kernel's ladder that enqueue_pedersen_impl gives a launch of n
+// hashes, when that launch is one of the single-launch kernels at one wave per SIMD: 0..2 = the fused lane-split
+// kernel of log_l = s, 3..5 = the quad kernel of log_q = s - 2.  -1: any other launch.
+static int tail_lane_class(size_t n, int nwin) {
+  const QuadShape q = quad_shape(n, nwin);
+  if (q.log_q != 0) return 2 + q.log_q;
+  const int log_l = split_log_l(n, nwin);
+  const bool one_launch = g_split_enabled && g_fuse_enabled && log_l <= 2 && (n << log_l) <= 65536;
+  return one_launch ? log_l : -1;
+}
+
 static int enqueue_pedersen_impl(const uint64_t* x, size_t xs, const uint64_t* y, size_t ys, uint64_t* out,
                                  size_t os, uint8_t* status, unsigned* flag, size_t n, hipStream_t st,
                                  const Scratch& s, const int2* src, const aff_packed* cpts);
@@ -1230,6 +1332,7 @@ int enqueue_pedersen_sparse(const uint64_t* x, const uint64_t* y, uint64_t* out,
 }
 static bool g_path_fusion = getenv("STARKPERP_NO_PATH_FUSION") == nullptr;  // A/B switch
 static bool g_top_fusion = getenv("STARKPERP_NO_TOP_FUSION") == nullptr;    // A/B switch
+static bool g_tail_fusion = getenv("STARKPERP_NO_TAIL_FUSION") == nullptr;  // A/B switch
 static bool g_chain_fusion = getenv("STARKPERP_NO_CHAIN_FUSION") == nullptr;  // A/B switch
 // n chains of `steps` hashes each as one launch (ped_chain_kernel); *done = false when n is not of a size class the
 // quad kernels serve or there is a single step: the caller enqueues the steps one by one.
@@ -1252,10 +1355,28 @@ int enqueue_pedersen_chain(const uint64_t* first, const uint64_t* words, long lo
 // Up to four consecutive small levels of a dense forest as one launch (ped_top_kernel): `cur` = the level-major
 // buffer at a level of n_in nodes, `remaining` = levels left inside every tree.  Returns the number of levels
 // enqueued (0: not this size class, the caller enqueues one level the usual way).
+//
+// From the first level that fits one wave per SIMD the levels go out 9 - s0 at a time (ped_tail_kernel, s0 = the lane
+// class of that level: 512 >> s0 nodes per block down to one) when every tree holds whole blocks at that level and
+// every level of the launch has the lane class of the kernel's ladder - which the default switches give.  The
+// eight-quad class (s0 = 5) stays with ped_top_kernel: there the two kernels are the same loop.
 int enqueue_pedersen_top(uint64_t* cur, size_t n_in, unsigned remaining, unsigned* flag, hipStream_t st, int* levels_done) {
   *levels_done = 0;
   Context& c = ctx();
   const int nwin = c.plan.nwin;
+  if (g_tail_fusion && nwin >= 16 && nwin <= 64 && n_in >= 2) {
+    const int s0 = tail_lane_class(n_in / 2, nwin);
+    const int L = 9 - s0;
+    bool take = s0 >= 0 && s0 <= 4 && remaining >= (unsigned)L;  // 2^remaining nodes per tree, 2^L per block
+    for (int t = 1; take && t < L; ++t) take = tail_lane_class(n_in >> (t + 1), nwin) == (s0 + t < 5 ? s0 + t : 5);
+    if (take) {
+      hipLaunchKernelGGL(ped_tail_kernel, dim3((unsigned)(n_in >> L)), dim3(256), 0, st, cur, n_in, s0, L, c.ped,
+                         (int)c.plan.bits[0], c.plan.log2e, nwin, flag);
+      SP_HIP(hipGetLastError());
+      *levels_done = L;
+      return SP_OK;
+    }
+  }
   if (!g_top_fusion || !g_quad_enabled || nwin > 64 || nwin < 16 || remaining < 2 || n_in / 2 > g_quad_max || n_in < 4) return SP_OK;
   const int L = remaining < 4 ? (int)remaining : 4;
   const unsigned blocks = (unsigned)(n_in >> L);  // every tree holds a whole number of 2^L-node chunks at this level
@@ -1302,14 +1423,8 @@ static int enqueue_pedersen_impl(const uint64_t* x, size_t xs, const uint64_t* y
   // lanes at L = 2 take 88 us, 40 960 hashes at L = 1 65 us), so the hashes are split over as many lanes
   // as still fit ONE wave per SIMD (65 536 lanes).  Every lane needs at least two windows.
   const int w0 = c.plan.bits[0], log2e = c.plan.log2e, nwin = c.plan.nwin;
-  int log_l = 0;
+  const int log_l = split_log_l(n, nwin);
   bool fused = false;
-  if (g_split_enabled) {
-    if (n * 8 <= g_split_lanes) log_l = 3;
-    else if (n * 4 <= g_split_lanes) log_l = 2;
-    else if (n * 2 <= g_split_lanes) log_l = 1;
-    while (log_l > 0 && nwin < (2 << log_l)) --log_l;
-  }
   // quad-parallel latency kernels while the level fits one wave per SIMD (quad_shape)
   const QuadShape q = quad_shape(n, nwin);
   if (q.log_q != 0) {
@@ -1913,12 +2028,14 @@ int sp_merkle_forest_dev(uint64_t* levels, size_t n_trees, unsigned height, uint
   Scratch s;
   int rc = get_scratch(n0 / 2 + 1, s, st);
   if (rc != SP_OK) return rc;
-  SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
+  // nobody reads the flag of a call without `status`: no fill launch in front of the first kernel, no flag
+  unsigned* flag = status ? s.flag : nullptr;
+  if (flag) SP_HIP(hipMemsetAsync(flag, 0, sizeof(unsigned), st));
   uint64_t* cur = levels;
   size_t n = n0;
   for (unsigned k = 0; k < height;) {
-    int fused = 0;  // the small levels go out four at a time (ped_top_kernel)
-    rc = enqueue_pedersen_top(cur, n, height - k, s.flag, st, &fused);
+    int fused = 0;  // the one-wave levels go out several at a time (ped_tail_kernel, ped_top_kernel)
+    rc = enqueue_pedersen_top(cur, n, height - k, flag, st, &fused);
     if (rc != SP_OK) return rc;
     if (fused > 0) {
       for (int j = 0; j < fused; ++j, n >>= 1) cur += 4 * n;
@@ -1926,13 +2043,13 @@ int sp_merkle_forest_dev(uint64_t* levels, size_t n_trees, unsigned height, uint
       continue;
     }
     uint64_t* nxt = cur + 4 * n;
-    rc = enqueue_pedersen(cur, 2, cur + 4, 2, nxt, 1, nullptr, s.flag, n / 2, st, s, nullptr);
+    rc = enqueue_pedersen(cur, 2, cur + 4, 2, nxt, 1, nullptr, flag, n / 2, st, s, nullptr);
     if (rc != SP_OK) return rc;
     cur = nxt;
     ++k;
     n >>= 1;
   }
-  if (status) SP_HIP(hipMemcpyAsync(status, s.flag, 1, hipMemcpyDeviceToHost, st));
+  if (status) SP_HIP(hipMemcpyAsync(status, flag, 1, hipMemcpyDeviceToHost, st));
   return SP_OK;
 }
 
