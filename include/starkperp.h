@@ -98,7 +98,8 @@ int sp_init(int device, int window_bits);
  *     one contiguous slice per context, the slices running side by side on host threads of the library; sp_pedersen_batch_dev, sp_pedersen_chains_dev, sp_pedersen_chains_ragged_dev, sp_merkle_fold_paths_dev, sp_merkle_build_dev, sp_merkle_forest_dev,
  *     sp_commit_rows_dev, sp_ecdsa_verify_batch_dev, sp_ecdsa_sign_batch_dev, sp_ecdsa_sign_rfc6979_batch_dev,
  *     sp_public_key_batch_dev, sp_felt_sqrt_batch_dev, sp_stark_key_y_batch_dev, sp_ec_mult_batch_dev,
- *     sp_ec_lincomb_batch_dev and sp_ec_add_batch_dev run on the device their pointers
+ *     sp_ec_lincomb_batch_dev, sp_ec_add_batch_dev and sp_commit_open_dev (sp_commit_open too: its tables are
+ *     device pointers) run on the device their pointers
  *     live on (the stream
  *     must belong to that device);
  *   - everything with state - persistent trees, key tables, the prover entry points (twiddle tables, witness
@@ -127,7 +128,7 @@ const char* sp_build_info(void);
  * (ped_accumulate_kernel) is bracketed by HIP events on the stream it is launched on; _end returns
  * the summed kernel time, the number of launches and the number of hashes they processed.  The launches of
  * sp_felt_sqrt_batch*, sp_stark_key_y_batch* and the three sp_ec_*_batch* calls are bracketed the same way (units:
- * items). */
+ * items), and so are those of sp_commit_open* (units: openings). */
 int sp_profile_begin(size_t max_launches);
 int sp_profile_end(double* total_ms, uint64_t* launches, uint64_t* units);
 
@@ -759,6 +760,49 @@ int sp_coset_eval_dev(const uint64_t* coef, uint64_t* out, unsigned ncols, unsig
  * pointer makes the call wait for the stream. */
 int sp_commit_rows_dev(const uint64_t* cols, size_t n_rows, size_t n_cols, uint64_t* levels, uint8_t* status,
                        void* stream);
+/* Opening committed tables: the prover's half of the query phase.  ONE launch (commit_open_kernel) reads every
+ * opened row and every Merkle sibling of a call out of tables that sp_commit_rows_dev committed, and writes the
+ * layout that sp_merkle_fold_paths / sp_merkle_verify_paths take in their off != NULL form - as sp_tree_prove does
+ * for the persistent trees.
+ *   table t       cols[t]: DEVICE pointer to n_rows[t] x n_cols[t] felts, column-major, column c starting
+ *                 c * col_stride[t] felts in (col_stride[t] >= n_rows[t]; n_rows[t] a power of two, 1 .. 2^32;
+ *                 n_cols[t] >= 1); levels[t]: DEVICE pointer to the 2 n_rows[t] - 1 felts sp_commit_rows_dev wrote,
+ *                 leaves first, root last.  The arrays cols, col_stride, n_rows, n_cols, levels themselves, table_of
+ *                 and rows are HOST arrays (n_tables and n_open entries)
+ *   opening i     row r = rows[i] of table t = table_of[i], h = log2 n_rows[t]:
+ *                 values + 4 val_off[i]   n_cols[t] felts, the row's value in each column, in column order
+ *                 leaves + 4 i            levels[t][r]  (leaves may be NULL: not wanted)
+ *                 siblings + 4 off[i]     h felts, sibling l = levels[t][base_l + ((r >> l) ^ 1)] with
+ *                                         base_l = 2 n_rows - (2 n_rows >> l); a table of one row has none
+ *   val_off, off  HOST arrays of n_open + 1 entries that the call FILLS (val_off[0] = off[0] = 0), in felts
+ * so (leaves, siblings, off, keys = rows) is, unchanged, the input of sp_merkle_fold_paths / sp_merkle_verify_paths.
+ * Duplicated and unordered openings are legal, each answered in its own slot.  sp_commit_open_size gives the two
+ * totals (felts of values, felts of siblings) from the shapes alone; it needs no device.
+ * SP_ERR_BAD_ARGUMENT, before anything is launched or written, sp_last_error() naming the argument: n_tables == 0
+ * with n_open > 0; a NULL table pointer (or a NULL array that is needed); n_rows of 0, not a power of two or above
+ * 2^32; n_cols == 0; col_stride < n_rows (or so large that n_cols columns leave the address space); table_of[i] >=
+ * n_tables; rows[i] >= n_rows; more than 2^32 - 1 value felts or sibling felts in total; a NULL required output
+ * (val_off, off; values; siblings if any table has more than one row).  n_open == 0 is SP_OK with both offset
+ * arrays = {0}.
+ * The context is the one of the device cols[0] lives on; all tables of one call live there.  The _dev call takes
+ * values, leaves and siblings on the device, enqueues on `stream` and waits for nothing; the host arrays have been
+ * copied when it returns.  sp_commit_open takes them as HOST arrays: it runs on a host lane of that context and
+ * brings the three back in ONE device-to-host copy through the lane's page-locked buffer (above 4 MiB: one direct
+ * copy per array); the lane's stream waits for no other, so the stream that committed the tables must have drained.  One launch serves up to 65536 openings, the largest class; above that consecutive slices go out
+ * on the same stream.  The launches are bracketed by sp_profile_begin / sp_profile_end (units: openings).
+ * Not capturable into a graph on first use: the per-stream metadata buffer (48 bytes per table, 20 per opening) and
+ * the stream's page-locked staging buffer grow on demand, as the host lane's buffers do.
+ * Measured: profiles/open_queries.txt (tools/quick_open_queries.py). */
+int sp_commit_open_size(size_t n_tables, const size_t* n_rows, const size_t* n_cols, size_t n_open,
+                        const uint32_t* table_of, size_t* n_values, size_t* n_siblings);
+int sp_commit_open_dev(size_t n_tables, const void* const* cols, const size_t* col_stride, const size_t* n_rows,
+                       const size_t* n_cols, const void* const* levels, size_t n_open, const uint32_t* table_of,
+                       const uint64_t* rows, uint64_t* values, uint32_t* val_off, uint64_t* leaves, uint64_t* siblings,
+                       uint32_t* off, void* stream);
+int sp_commit_open(size_t n_tables, const void* const* cols, const size_t* col_stride, const size_t* n_rows,
+                   const size_t* n_cols, const void* const* levels, size_t n_open, const uint32_t* table_of,
+                   const uint64_t* rows, uint64_t* values, uint32_t* val_off, uint64_t* leaves, uint64_t* siblings,
+                   uint32_t* off);
 
 #ifdef __cplusplus
 }

@@ -292,6 +292,80 @@ def _gather_felts(t, indices):
     return tensor_to_felts(t.index_select(0, idx))
 
 
+def _table_shape(cols):
+    """(n_rows, n_cols, col_stride in felts) of a committed table: [n_cols, n_rows, 4] or one column [n_rows, 4]."""
+    if cols.dim() == 2:
+        cols = cols.unsqueeze(0)
+    assert cols.dim() == 3 and cols.shape[2] == 4 and cols.stride(2) == 1 and cols.stride(1) == 4
+    stride = cols.stride(0) // 4 if cols.shape[0] > 1 else cols.shape[1]
+    assert cols.stride(0) % 4 == 0 and stride >= cols.shape[1]
+    return cols.shape[1], cols.shape[0], stride
+
+
+def open_rows(tables, picks, host_call: bool = False):
+    """The query phase's reads, all of them in one go: tables = [(cols, levels)] as committed by commit_rows (cols
+    [n_cols, n_rows, 4] or a single column [n_rows, 4]; levels the tensor commit_rows returned), picks = [(table,
+    row)].  Returns per pick (values, leaf, path) as Python ints: the row's value in every column, its leaf in the
+    tree and the siblings from the leaves' level up - what _open_by_slices reads with one round trip per value and
+    per path.  ONE sp_commit_open_dev call on the current stream and one download; host_call=True takes the
+    library's host-pointer call instead (its own lane, one staged copy back; the current stream is drained first)."""
+    import ctypes
+    import numpy as np
+    torch = _torch()
+    lib = _lib.ensure_init()
+    n_t, n = len(tables), len(picks)
+    if n == 0:
+        return []
+    shapes = [_table_shape(c) for c, _ in tables]
+    for (rows_t, _, _), (_, lv) in zip(shapes, tables):
+        assert lv.shape[0] == 2 * rows_t - 1 and lv.is_contiguous()
+    ptrs = lambda vals: (ctypes.c_void_p * max(n_t, 1))(*vals)
+    sizes = lambda vals: (ctypes.c_size_t * max(n_t, 1))(*vals)
+    cols_p, lv_p = ptrs([c.data_ptr() for c, _ in tables]), ptrs([lv.data_ptr() for _, lv in tables])
+    n_rows, n_cols, strides = (sizes([sh[k] for sh in shapes]) for k in range(3))
+    table_of = np.array([t for t, _ in picks], dtype=np.uint32)
+    rows = np.array([r for _, r in picks], dtype=np.uint64)
+    nv, ns = ctypes.c_size_t(), ctypes.c_size_t()
+    _lib.check(lib.sp_commit_open_size(n_t, n_rows, n_cols, n, table_of.ctypes.data, ctypes.byref(nv), ctypes.byref(ns)),
+               "sp_commit_open_size")
+    nv, ns = nv.value, ns.value
+    val_off, off = np.zeros(n + 1, dtype=np.uint32), np.zeros(n + 1, dtype=np.uint32)
+    # one buffer: values | leaves | siblings
+    if host_call:
+        out = np.zeros((nv + n + ns, 4), dtype=np.uint64)
+        base = out.ctypes.data
+    else:
+        out = torch.empty((nv + n + ns, 4), dtype=torch.int64, device=tables[0][0].device)
+        base = out.data_ptr()
+    args = (n_t, cols_p, strides, n_rows, n_cols, lv_p, n, table_of.ctypes.data, rows.ctypes.data, base,
+            val_off.ctypes.data, base + 32 * nv, base + 32 * (nv + n), off.ctypes.data)
+    if host_call:
+        torch.cuda.current_stream().synchronize()  # the lane's stream does not wait for the one that committed
+        _lib.check(lib.sp_commit_open(*args), "sp_commit_open")
+        raw = out.tobytes()
+    else:
+        _lib.check(lib.sp_commit_open_dev(*args, _stream()), "sp_commit_open_dev")
+        raw = out.cpu().numpy().tobytes()  # the one download; it waits for the stream
+    felts = [int.from_bytes(raw[32 * i : 32 * i + 32], "little") for i in range(nv + n + ns)]
+    val_off, off, sib = val_off.tolist(), off.tolist(), nv + n
+    return [(felts[val_off[i] : val_off[i + 1]], felts[nv + i], felts[sib + off[i] : sib + off[i + 1]])
+            for i in range(n)]
+
+
+def _open_by_slices(tables, picks):
+    """What open_rows returns, read the way the query phase read it before sp_commit_open: every value with its own
+    slice and synchronous download, every path with its own index upload, gather and download.  Kept as the
+    in-process reference of open_rows (tests/test_gpu_commit_open.py)."""
+    out = []
+    for t, row in picks:
+        cols, lv = tables[t]
+        if cols.dim() == 2:
+            cols = cols.unsqueeze(0)
+        values = [tensor_to_felts(cols[c][row : row + 1])[0] for c in range(cols.shape[0])]
+        out.append((values, tensor_to_felts(lv[row : row + 1])[0], _gather_felts(lv, _path_indices(cols.shape[1], row))))
+    return out
+
+
 def prove(xs, ys, n_queries: int = 8, seed: int = 0, final_log: int = 6, shift: int = FIELD_GEN):
     """Benchmark-grade argument (NOT a sound proof system) that the trace of the hashes (xs[i], ys[i])
     satisfies the Pedersen-step AIR: see prove_trace for what is and is not bound."""
@@ -345,6 +419,12 @@ def prove_trace(trace, air: str, n_queries: int = 8, seed: int = 0, final_log: i
     constraint binds the hash inputs / outputs (or `public_inputs`, which are only absorbed), there is
     no zero knowledge, and the default 8 queries at blowup 4 give about 16 bits.  The reference has no
     prover; this path is build-defined and benchmark-grade."""
+    return _query_trace(_commit_trace(trace, air, seed, final_log, shift, public_inputs), n_queries)
+
+
+def _commit_trace(trace, air, seed, final_log, shift, public_inputs):
+    """The commit phase of prove_trace: every commitment, the transcript up to the final layer.  Returns what the
+    query phase needs."""
     P = FIELD_PRIME
     spec = AIRS[air]
     n = trace.shape[1]
@@ -373,27 +453,51 @@ def prove_trace(trace, air: str, n_queries: int = 8, seed: int = 0, final_log: i
             break
     final = tensor_to_felts(layers[-1])
     tr.absorb("final_layer", *final)
-    queries = []
-    for q in range(n_queries):
-        j = tr.challenge("query", q, modulus=M // 2)
-        entry = {"index": j, "trace": [], "layers": []}
+    return {"tr": tr, "M": M, "trace_lde": trace_lde, "lv_trace": lv_trace, "layers": layers, "level_bufs": level_bufs,
+            "head": {"n": n, "air": air, "seed": seed, "shift": shift, "public_inputs": list(public_inputs),
+                     "trace_root": root_t, "layer_roots": roots, "final_layer": final}}
+
+
+def _layer_positions(j, layers):
+    """The pair of positions a query at index j opens in every committed FRI layer."""
+    out, jk = [], j
+    for layer in layers:
+        mk = layer.shape[0]
+        jk %= mk // 2
+        out.append((jk, jk + mk // 2))
+    return out
+
+
+def _query_trace(c, n_queries, opener=None):
+    """The query phase of prove_trace on the state _commit_trace returned: the positions are drawn first (host-only
+    transcript work), every pick of the proof - four trace rows and one pair per layer for each query - goes to ONE
+    opener call (open_rows; _open_by_slices is the reference), then the dict is assembled."""
+    opener = opener or open_rows
+    M, layers = c["M"], c["layers"][:-1]
+    tables = [(c["trace_lde"], c["lv_trace"])] + list(zip(layers, c["level_bufs"]))
+    indices = [c["tr"].challenge("query", q, modulus=M // 2) for q in range(n_queries)]
+    picks = []
+    for j in indices:
         for pos in (j, j + M // 2):
             for row in (pos, (pos + (1 << BLOWUP_LOG)) % M):
-                vals = [tensor_to_felts(trace_lde[c][row : row + 1])[0] for c in range(spec["n_cols"])]
-                entry["trace"].append({"row": row, "values": vals,
-                                       "path": _gather_felts(lv_trace, _path_indices(M, row))})
-        jk = j
-        for k, (layer, lv) in enumerate(zip(layers[:-1], level_bufs)):
-            mk = layer.shape[0]
-            jk %= mk // 2
+                picks.append((0, row))
+        for k, pair in enumerate(_layer_positions(j, layers)):
+            picks += [(1 + k, pos) for pos in pair]
+    opened = iter(zip(picks, opener(tables, picks)))
+    queries = []
+    for j in indices:
+        entry = {"index": j, "trace": [], "layers": []}
+        for _ in range(4):
+            (_, row), (values, _, path) = next(opened)
+            entry["trace"].append({"row": row, "values": values, "path": path})
+        for _ in layers:
             pair = []
-            for pos in (jk, jk + mk // 2):
-                pair.append({"pos": pos, "value": tensor_to_felts(layer[pos : pos + 1])[0],
-                             "path": _gather_felts(lv, _path_indices(mk, pos))})
+            for _ in range(2):
+                (_, pos), (values, _, path) = next(opened)
+                pair.append({"pos": pos, "value": values[0], "path": path})
             entry["layers"].append(pair)
         queries.append(entry)
-    return {"n": n, "air": air, "seed": seed, "shift": shift, "public_inputs": list(public_inputs),
-            "trace_root": root_t, "layer_roots": roots, "final_layer": final, "queries": queries}
+    return dict(c["head"], queries=queries)
 
 
 def check_merkle_openings(proof) -> List[Tuple[str, bool]]:
@@ -541,6 +645,13 @@ def prove_builtins(hash_inputs=None, signatures=None, rc_values=None, n_queries:
     challenge z - the permutation product of the range-check segment.  Benchmark-grade like prove_trace (no
     boundary constraint ties the instances to the public inputs except rc_min / rc_max; ~2 bits per query).
     Verifier: oracle/stark_ref.verify_builtins_proof."""
+    return _query_builtins(_commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift, log_rows),
+                           n_queries)
+
+
+def _commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift, log_rows):
+    """The commit phase of prove_builtins (both committed phases, the composition, the FRI layers); returns what the
+    query phase needs."""
     torch = _torch()
     dev = "cuda"
     P = FIELD_PRIME
@@ -628,26 +739,46 @@ def prove_builtins(hash_inputs=None, signatures=None, rc_values=None, n_queries:
             break
     final = tensor_to_felts(layers[-1])
     tr.absorb("final_layer", *final)
-    queries = []
-    for q in range(n_queries):
-        j = tr.challenge("query", q, modulus=M // 2)
-        entry = {"index": j, "phase1": [], "phase2": [], "layers": []}
+    return {"tr": tr, "M": M, "trace_lde": trace_lde, "lv1": lv1, "p_lde": p_lde, "lv2": lv2, "layers": layers,
+            "level_bufs": level_bufs,
+            "head": {"n": n, "air": "builtins", "segments": segments, "seed": seed, "shift": shift,
+                     "public_inputs": public, "phase1_root": root1, "phase2_root": root2, "layer_roots": roots,
+                     "final_layer": final}}
+
+
+def _query_builtins(c, n_queries, opener=None):
+    """The query phase of prove_builtins, shaped as _query_trace: per query four phase-1 rows, the same four rows of
+    phase 2 when it exists, one pair per layer - all picks of the proof in ONE opener call."""
+    opener = opener or open_rows
+    M, layers, two = c["M"], c["layers"][:-1], c["lv2"] is not None
+    tables = [(c["trace_lde"], c["lv1"])] + ([(c["p_lde"], c["lv2"])] if two else [])
+    first_layer = len(tables)
+    tables += list(zip(layers, c["level_bufs"]))
+    indices = [c["tr"].challenge("query", q, modulus=M // 2) for q in range(n_queries)]
+    picks = []
+    for j in indices:
         for pos in (j, j + M // 2):
             for row in (pos, (pos + (1 << BLOWUP_LOG)) % M):
-                entry["phase1"].append({"row": row, "values": tensor_to_felts(trace_lde[:, row]),
-                                        "path": _gather_felts(lv1, _path_indices(M, row))})
-                if rc_values:
-                    entry["phase2"].append({"row": row, "value": tensor_to_felts(p_lde[row : row + 1])[0],
-                                            "path": _gather_felts(lv2, _path_indices(M, row))})
-        jk = j
-        for k, (layer, lv) in enumerate(zip(layers[:-1], level_bufs)):
-            mk = layer.shape[0]
-            jk %= mk // 2
+                picks.append((0, row))
+                if two:
+                    picks.append((1, row))
+        for k, pair in enumerate(_layer_positions(j, layers)):
+            picks += [(first_layer + k, pos) for pos in pair]
+    opened = iter(zip(picks, opener(tables, picks)))
+    queries = []
+    for j in indices:
+        entry = {"index": j, "phase1": [], "phase2": [], "layers": []}
+        for _ in range(4):
+            (_, row), (values, _, path) = next(opened)
+            entry["phase1"].append({"row": row, "values": values, "path": path})
+            if two:
+                (_, row), (values, _, path) = next(opened)
+                entry["phase2"].append({"row": row, "value": values[0], "path": path})
+        for _ in layers:
             pair = []
-            for pos in (jk, jk + mk // 2):
-                pair.append({"pos": pos, "value": tensor_to_felts(layer[pos : pos + 1])[0],
-                             "path": _gather_felts(lv, _path_indices(mk, pos))})
+            for _ in range(2):
+                (_, pos), (values, _, path) = next(opened)
+                pair.append({"pos": pos, "value": values[0], "path": path})
             entry["layers"].append(pair)
         queries.append(entry)
-    return {"n": n, "air": "builtins", "segments": segments, "seed": seed, "shift": shift, "public_inputs": public,
-            "phase1_root": root1, "phase2_root": root2, "layer_roots": roots, "final_layer": final, "queries": queries}
+    return dict(c["head"], queries=queries)
