@@ -804,6 +804,50 @@ int sp_commit_open(size_t n_tables, const void* const* cols, const size_t* col_s
                    const uint64_t* rows, uint64_t* values, uint32_t* val_off, uint64_t* leaves, uint64_t* siblings,
                    uint32_t* off);
 
+/* Verifying a proof: the field arithmetic of a verifier of stark.prove_trace's proofs, on opened values only.  Both
+ * calls take DEVICE arrays of packed felts, the challenges and the shift as HOST felts, enqueue ONE launch on
+ * `stream` (one item per lane, grids from the item count alone; bracketed by sp_profile_begin / sp_profile_end) and
+ * wait for nothing.  Neither builds or reads a table that grows with the trace: the periodic table has 4 * period
+ * rows, and a fold item derives its own point of the coset.  A count of 0 is SP_OK without a launch; a NULL pointer
+ * with a count above 0, an unknown `air`, a violated bound or a bad shift is SP_ERR_BAD_ARGUMENT before anything is
+ * launched or written.  At most 2^30 items per call.
+ *
+ * sp_air_eval_points_dev: the composition value sum_k alpha_k C_k / Z_H at n_points LDE positions of the AIR `air`
+ *   (SP_AIR_*), exactly what the dense call of that AIR (sp_air_eval_dev, sp_air_eval_ec_ladder_dev,
+ *   sp_air_eval_ecdsa_dev, sp_air_eval_range_check_dev) writes at index pos[i].  log_n, periodic_lde, alphas_host
+ *   and shift_host are the dense call's, with its bounds on log_n and its rule on the shift.
+ *     pos[i]     LDE index below M = 4 * 2^log_n (u64)
+ *     cur, nxt   n_points x n_cols felts, row-major: the trace row at pos[i] and the one at (pos[i] + 4) mod M
+ *     out[i]     the value;  status[i] = SP_POINT_OK, or SP_POINT_OUT_OF_RANGE with out[i] = 0 when pos[i] >= M or
+ *                a felt of the two rows is not below p (nothing is read out of bounds for any pos[i])
+ * sp_fri_check_queries_dev: the fold chain of n_queries queries through n_layers committed FRI layers, layer 0 of
+ *   2^log_m points on shift * <w>; 1 <= n_layers < log_m <= 32.
+ *     index[q]      the query's index below 2^(log_m - 1) (u64)
+ *     pairs         n_queries x n_layers x 2 felts: the two opened values of layer k, at jk = index[q] mod
+ *                   2^(log_m - k - 1) and at jk + 2^(log_m - k - 1)
+ *     final_layer   2^(log_m - n_layers) felts;  betas_host: n_layers felts
+ *     status[q * n_layers + k]   with x = shift^(2^k) w_{2^(log_m - k)}^jk and
+ *                   folded = (a + b) / 2 + beta_k (a - b) / (2 x): SP_FOLD_OK when folded equals the member
+ *                   (jk < 2^(log_m - k - 2) ? 0 : 1) of the pair of layer k + 1 - final_layer[jk] after the last
+ *                   layer -, SP_FOLD_MISMATCH when it does not, SP_FOLD_OUT_OF_RANGE when a, b or that value is not
+ *                   below p or index[q] >= 2^(log_m - 1) (then for every layer of the query)
+ * What a verifier does around them - transcript, Merkle paths, the final layer's degree - is starkperp.stark.verify. */
+#define SP_AIR_PEDERSEN 0
+#define SP_AIR_EC_LADDER 1
+#define SP_AIR_ECDSA 2
+#define SP_AIR_RANGE_CHECK 3
+#define SP_POINT_OK 0
+#define SP_POINT_OUT_OF_RANGE 1
+#define SP_FOLD_OK 0
+#define SP_FOLD_MISMATCH 1
+#define SP_FOLD_OUT_OF_RANGE 2
+int sp_air_eval_points_dev(int air, unsigned log_n, const uint64_t* periodic_lde, const uint64_t* alphas_host,
+                           const uint64_t* shift_host, size_t n_points, const uint64_t* pos, const uint64_t* cur,
+                           const uint64_t* nxt, uint64_t* out, uint8_t* status, void* stream);
+int sp_fri_check_queries_dev(unsigned log_m, unsigned n_layers, const uint64_t* shift_host, const uint64_t* betas_host,
+                             size_t n_queries, const uint64_t* index, const uint64_t* pairs,
+                             const uint64_t* final_layer, uint8_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

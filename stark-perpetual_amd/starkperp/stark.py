@@ -384,8 +384,8 @@ def prove_ecdsa(msg_hashes, rs, ss, public_keys, n_queries: int = 8, seed: int =
     """Benchmark-grade argument (NOT a sound proof system) that every (z, r, s, Q) passes the reference's
     verify (signature.py:217-260: the three ladders, the two additions, x == r).  Python ints in; the
     count must be a power of two.  w = s^-1 mod N is computed here as verify() does (:220) and the public
-    inputs (z, r, s, Qx, Qy per signature) are absorbed into the transcript; the CPU verifier
-    (oracle/stark_ref.verify_proof) re-derives w from s."""
+    inputs (z, r, s, Qx, Qy per signature) are absorbed into the transcript; the verifier (verify, and its oracle
+    oracle/stark_ref.verify_proof) re-derives w from s."""
     dev = "cuda"
     ws = [pow(s, -1, EC_ORDER) for s in ss]
     for z, r, w in zip(msg_hashes, rs, ws):
@@ -411,7 +411,7 @@ def prove_range_checks(values, n_queries: int = 8, seed: int = 0, final_log: int
 def prove_trace(trace, air: str, n_queries: int = 8, seed: int = 0, final_log: int = 6,
                 shift: int = FIELD_GEN, public_inputs=()):
     """Commitments to the trace LDE, the composition column and every FRI layer, the final layer in
-    the clear, and for each query the openings a verifier needs (oracle/stark_ref.verify_proof).
+    the clear, and for each query the openings a verifier needs (verify; oracle/stark_ref.verify_proof is its oracle).
 
     What this is: the prover-side workload of BASELINE.json configs[3] made checkable end to end.  The
     Fiat-Shamir transcript is chained (statement, then every commitment in order; alpha, every beta and
@@ -512,8 +512,8 @@ def check_merkle_openings(proof) -> List[Tuple[str, bool]]:
     A value outside [0, p) makes its opening False.
 
     This checks the Merkle part ONLY.  The AIR relation between the opened rows and the composition column, the FRI
-    fold consistency, the final layer's degree, the query positions and the transcript stay with
-    oracle/stark_ref.verify_proof: a proof whose openings are all True here can still be rejected there."""
+    fold consistency, the final layer's degree, the query positions and the transcript are verify()'s, which calls
+    this for its Merkle part: a proof whose openings are all True here can still be rejected there."""
     import numpy as np
     from . import batch_np
     P = FIELD_PRIME
@@ -562,6 +562,228 @@ def check_merkle_openings(proof) -> List[Tuple[str, bool]]:
                                               offsets=off)
     ok = verdict & fits & ~leaf_bad
     return list(zip(labels, [bool(v) for v in ok]))
+
+
+# ---- the verifier ---------------------------------------------------------------------------------------------
+# Product twin of oracle/stark_ref.verify_proof: the same checks in the same order with the same reasons.  The
+# transcript (SHA-256) and the comparisons of positions run on the host; every hash goes through the chain and path
+# calls of check_merkle_openings, the composition values and the fold chains through the two calls of csrc/verify.hip,
+# the final layer's interpolation through ntt.
+AIR_IDS = {"pedersen": 0, "ec_ladder": 1, "ecdsa": 2, "range_check": 3}  # SP_AIR_* of include/starkperp.h
+POINT_OK, POINT_OUT_OF_RANGE = 0, 1
+FOLD_OK, FOLD_MISMATCH, FOLD_OUT_OF_RANGE = 0, 1, 2
+
+
+def air_eval_points(air, n, per_lde, alphas, shift, pos, cur, nxt):
+    """The composition value at arbitrary LDE positions from opened rows (sp_air_eval_points_dev): pos [k] int64
+    tensor of LDE indices, cur / nxt [k, n_cols, 4] the rows at pos and at (pos + 4) mod 4n.  Returns (out [k, 4],
+    status [k] uint8): what air_eval writes at those indices, and POINT_OK / POINT_OUT_OF_RANGE per point."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    spec = AIRS[air]
+    k = pos.shape[0]
+    assert len(alphas) == spec["n_constraints"] and tuple(cur.shape) == tuple(nxt.shape) == (k, spec["n_cols"], 4)
+    assert pos.dtype == torch.int64 and pos.is_contiguous() and cur.is_contiguous() and nxt.is_contiguous()
+    out = torch.empty((k, 4), dtype=torch.int64, device=cur.device)
+    status = torch.empty((k,), dtype=torch.uint8, device=cur.device)
+    _lib.check(lib.sp_air_eval_points_dev(AIR_IDS[air], n.bit_length() - 1, per_lde.data_ptr(), pack_felts(alphas),
+                                          pack_felts([shift]), k, pos.data_ptr(), cur.data_ptr(), nxt.data_ptr(),
+                                          out.data_ptr(), status.data_ptr(), _stream()), "sp_air_eval_points_dev")
+    return out, status
+
+
+def fri_check_queries(log_m, betas, shift, index, pairs, final_layer):
+    """The fold chain of every query (sp_fri_check_queries_dev): index [q] int64 tensor, pairs [q, n_layers, 2, 4]
+    the opened values of every layer, final_layer [2^(log_m - n_layers), 4].  Returns status [q, n_layers] uint8:
+    FOLD_OK / FOLD_MISMATCH / FOLD_OUT_OF_RANGE for the step from layer k to layer k + 1 (the final layer last)."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    q, n_layers = index.shape[0], len(betas)
+    assert tuple(pairs.shape) == (q, n_layers, 2, 4) and tuple(final_layer.shape) == (1 << (log_m - n_layers), 4)
+    assert index.dtype == torch.int64 and index.is_contiguous() and pairs.is_contiguous() and final_layer.is_contiguous()
+    status = torch.empty((q, n_layers), dtype=torch.uint8, device=pairs.device)
+    _lib.check(lib.sp_fri_check_queries_dev(log_m, n_layers, pack_felts([shift]), pack_felts(betas), q, index.data_ptr(),
+                                            pairs.data_ptr(), final_layer.data_ptr(), status.data_ptr(), _stream()),
+               "sp_fri_check_queries_dev")
+    return status
+
+
+def _is_int(v):
+    return type(v) is int
+
+
+def _is_felt(v):
+    return type(v) is int and 0 <= v < FIELD_PRIME
+
+
+def _felt_list(v, length=None):
+    return isinstance(v, (list, tuple)) and (length is None or len(v) == length) and all(_is_felt(x) for x in v)
+
+
+def _wellformed(proof):
+    """Whether `proof` has the keys and types of a prove_trace proof, every felt in [0, p), every integer an int: what
+    must hold before a value is hashed into the transcript or sent to the device.  Lengths that the oracle reports
+    as "shape" (layer_roots, final_layer) are left to verify."""
+    if not isinstance(proof, dict):
+        return False
+    air, n, shift = proof.get("air", "pedersen"), proof.get("n"), proof.get("shift")
+    if not isinstance(air, str) or air not in AIR_IDS:
+        return False
+    spec = AIRS[air]
+    if not (_is_int(n) and spec["period"] <= n <= 1 << 30 and n & (n - 1) == 0):
+        return False
+    # a shift with shift^(4n) = 1 puts the coset onto the trace domain: no composition column exists on it
+    if not (_is_felt(shift) and shift != 0 and pow(shift, 4 * n, FIELD_PRIME) != 1):
+        return False
+    if not (_is_int(proof.get("seed")) and 0 <= proof["seed"] < 1 << 256 and _is_felt(proof.get("trace_root"))):
+        return False
+    pub = proof.get("public_inputs", ())
+    if not (isinstance(pub, (list, tuple)) and all(_is_int(v) and 0 <= v < 1 << 256 for v in pub)):
+        return False
+    if not (_felt_list(proof.get("layer_roots")) and _felt_list(proof.get("final_layer"))):
+        return False
+    queries = proof.get("queries")
+    if not isinstance(queries, (list, tuple)):
+        return False
+    log_m = n.bit_length() + 1
+    for q in queries:
+        if not (isinstance(q, dict) and _is_int(q.get("index")) and isinstance(q.get("trace"), (list, tuple))
+                and isinstance(q.get("layers"), (list, tuple)) and len(q["trace"]) == 4):
+            return False
+        for t in q["trace"]:
+            if not (isinstance(t, dict) and _is_int(t.get("row")) and _felt_list(t.get("values"), spec["n_cols"])
+                    and _felt_list(t.get("path"), log_m)):
+                return False
+        for k, pair in enumerate(q["layers"]):
+            if not (isinstance(pair, (list, tuple)) and len(pair) == 2):
+                return False
+            for o in pair:
+                if not (isinstance(o, dict) and _is_int(o.get("pos")) and _is_felt(o.get("value"))
+                        and _felt_list(o.get("path"), max(log_m - k, 0))):
+                    return False
+    return True
+
+
+def _public_inputs_ok(air, n, pub):
+    """The statement rules of oracle/stark_ref.verify_proof for the AIRs that have public inputs."""
+    if air == "ecdsa":
+        from .signature import is_point_on_curve
+        if len(pub) != 5 * (n // 1024):
+            return False
+        for k in range(n // 1024):
+            z, r, sig_s, qx, qy = pub[5 * k : 5 * k + 5]
+            if not (1 <= sig_s < EC_ORDER and 1 <= r < 2**251 and 0 < z < 2**251 and is_point_on_curve(qx, qy)):
+                return False
+            if not 1 <= pow(sig_s, -1, EC_ORDER) < 2**251:
+                return False
+    if air == "range_check":
+        if len(pub) != n // RANGE_CHECK_BITS or not all(0 <= v < 2**RANGE_CHECK_BITS for v in pub):
+            return False
+    return True
+
+
+def verify(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]:
+    """Verifier of the proofs of prove_trace and its wrappers (prove, prove_ec_ladders, prove_ecdsa,
+    prove_range_checks): returns (ok, reason) with the reasons of oracle/stark_ref.verify_proof, the first failure
+    in that function's order - "public inputs", "shape", "final layer degree", then per query "query index", "trace
+    rows", "trace path", "composition value" and per layer "layer positions", "layer path", "fold consistency at
+    layer k" - or (True, "ok").  `final_log` is the prover's; a given `n_queries` must be the number of queries
+    ("shape").
+
+    Where it runs: the transcript (alphas, betas, query indices) and the comparisons of indices, rows and positions
+    on the host; every hash on the GPU through check_merkle_openings (two calls); the composition value of the 2 Q
+    opened points in ONE sp_air_eval_points_dev launch and the Q n_layers fold steps in ONE
+    sp_fri_check_queries_dev launch; the final layer's coefficients through ntt.  Everything is computed, then the
+    first failure is reported.
+
+    A malformed proof - a missing key, a non-integer, a felt outside [0, p), a path of the wrong length, an unknown
+    air, an n that is no power of two of at least the AIR's period, a shift that is 0 or puts the coset onto the
+    trace domain - returns (False, "malformed") before the library is initialised: nothing raises and no such value
+    reaches the device.  A prove_builtins proof (air == "builtins") raises ValueError: its verifier needs the
+    second-phase column and the challenge z and is a follow-up; oracle/stark_ref.verify_builtins_proof checks it.
+
+    The caveat of prove_trace holds here too: this verifies a benchmark-grade argument, NOT a sound proof system -
+    no boundary constraint binds the public inputs (they are only absorbed, and range-checked as the oracle does),
+    and Q queries at blowup 4 give about 2 Q bits."""
+    if isinstance(proof, dict) and proof.get("air") == "builtins":
+        raise ValueError("stark.verify does not take prove_builtins proofs yet (the builtins verifier is a follow-up; "
+                         "oracle/stark_ref.verify_builtins_proof checks them)")
+    try:
+        if not (_wellformed(proof) and _is_int(final_log) and 0 <= final_log <= 30):
+            return False, "malformed"
+    except Exception:  # an object that misbehaves when inspected is malformed too
+        return False, "malformed"
+    P = FIELD_PRIME
+    air, n, seed, shift = proof.get("air", "pedersen"), proof["n"], proof["seed"], proof["shift"]
+    spec = AIRS[air]
+    pub = list(proof.get("public_inputs", ()))
+    if not _public_inputs_ok(air, n, pub):
+        return False, "public inputs"
+    m = n << BLOWUP_LOG
+    log_m = m.bit_length() - 1
+    root_t, roots, final, queries = proof["trace_root"], proof["layer_roots"], proof["final_layer"], proof["queries"]
+    n_layers = log_m - final_log
+    if len(roots) != n_layers or len(final) != 1 << final_log or n_layers < 1:
+        return False, "shape"
+    if n_queries is not None and n_queries != len(queries):
+        return False, "shape"
+    if any(len(q["layers"]) != n_layers for q in queries):
+        return False, "malformed"
+    tr = Transcript(air, n, shift, seed, pub)
+    tr.absorb("trace_root", root_t)
+    alphas = [tr.challenge("alpha", k) for k in range(spec["n_constraints"])]
+    betas = []
+    for k in range(n_layers):
+        tr.absorb("layer_root", roots[k])
+        betas.append(tr.challenge("beta", k + 1))
+    tr.absorb("final_layer", *final)
+    indices = [tr.challenge("query", qi, modulus=m // 2) for qi in range(len(queries))]
+    # the final layer: its interpolant on shift^(2^n_layers) * <w> has the coefficients c_k shift'^k of the inverse
+    # transform over <w>, so the zero pattern is the same
+    torch = _torch()
+    final_t = felts_to_tensor(final)
+    coeffs = tensor_to_felts(ntt(final_t, inverse=True))
+    if any(c != 0 for c in coeffs[3 * n >> n_layers:]):
+        return False, "final layer degree"
+    if not queries:
+        return True, "ok"
+    openings = iter(check_merkle_openings(proof))
+    per = periodic_lde(n, shift, "cuda", air)
+    dev = per.device
+    positions = [pos for j in indices for pos in (j, j + m // 2)]
+    cur = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side]["values"]], dev)
+    nxt = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side + 1]["values"]], dev)
+    shape = (len(positions), spec["n_cols"], 4)
+    comp, comp_st = air_eval_points(air, n, per, alphas, shift, torch.tensor(positions, dtype=torch.int64, device=dev),
+                                    cur.reshape(shape), nxt.reshape(shape))
+    pairs = felts_to_tensor([o["value"] for q in queries for pair in q["layers"] for o in pair], dev)
+    fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
+                                pairs.reshape(len(queries), n_layers, 2, 4), final_t)
+    comp, comp_st, fold_st = tensor_to_felts(comp), comp_st.cpu().tolist(), fold_st.cpu().tolist()
+    for qi, (q, j) in enumerate(zip(queries, indices)):
+        trace_ok = [next(openings)[1] for _ in range(4)]
+        layer_ok = [[next(openings)[1] for _ in range(2)] for _ in range(n_layers)]
+        if q["index"] != j:
+            return False, "query index"
+        if [t["row"] for t in q["trace"]] != [j, (j + 4) % m, j + m // 2, (j + m // 2 + 4) % m]:
+            return False, "trace rows"
+        if not all(trace_ok):
+            return False, "trace path"
+        for side in (0, 1):
+            if comp_st[2 * qi + side] != POINT_OK or q["layers"][0][side]["value"] != comp[2 * qi + side]:
+                return False, "composition value"
+        jk, mk = j, m
+        for k in range(n_layers):
+            jk %= mk // 2
+            a, b = q["layers"][k]
+            if (a["pos"], b["pos"]) != (jk, jk + mk // 2):
+                return False, "layer positions"
+            if not all(layer_ok[k]):
+                return False, "layer path"
+            if fold_st[qi][k] != FOLD_OK:
+                return False, "fold consistency at layer %d" % k
+            mk //= 2
+    return True, "ok"
 
 
 # ---- the range-check builtin's encoding and ONE trace for the three builtins (SURVEY 8(f) N4) --------------------
