@@ -398,6 +398,22 @@ int sp_merkle_verify_update(unsigned height, const uint64_t* keys, size_t n, con
  * update of the orders tree `tree` with leaves[i] at order id i.  Verification and tree hashing overlap on the
  * device; the new nodes are committed only when every signature verified, otherwise *tree_status =
  * SP_TREE_NOT_COMMITTED and new_root = old_root.  Two orders with one id: SP_ERR_BAD_ARGUMENT.
+ * Pinned by tests/test_gpu_order_batch.py:
+ *   n == 0            SP_OK on a known tree: nothing is verified or written, *tree_status = 0, new_root = old_root
+ *                     (an unknown handle is SP_ERR_BAD_ARGUMENT also then).
+ *   tree_status       may be NULL; the outcome then shows as new_root == old_root.  z_out, verdicts, old_root and
+ *                     new_root are required.
+ *   a leaf >= p       *tree_status = SP_HASH_OUT_OF_RANGE (the byte of the tree's level hashing), nothing is
+ *                     committed, the verdicts are those of the signatures.  The hash byte wins over
+ *                     SP_TREE_NOT_COMMITTED: with a bad signature in the same batch the status is still the hash byte
+ *                     (the tree is refused before the verifier's answer is asked for).
+ *   a word >= p       at depth >= 2: *tree_status = the chains' SP_HASH_* byte, every verdict is 0, z_out is
+ *                     unspecified, new_root = old_root.  At depth 1 nothing is hashed: the word IS the message hash,
+ *                     and a word of 2^251 or more (>= p included) is SP_VERIFY_ASSERT_MSG as above.
+ *   order ids         must be below 2^height of the tree, else SP_ERR_BAD_ARGUMENT with the tree unchanged (like
+ *                     equal ids; z_out is written, the verdicts are unspecified).  id_shift <= 192, depth >= 1.
+ *   a z >= 2^251      the batch ends after the verification: ids are not formed, so neither equal ids nor a leaf >= p
+ *                     is reported beside it.
  * Host side: the verification runs on a thread of the call's own (spawned as soon as the message hashes are back,
  * parked until the tree update - the critical path - has enqueued its levels; joined before the call returns);
  * 4096 orders on a tree that holds state: 1.75 - 1.85 ms median, p90 within 7 %, against 1.51 ms of dependent
