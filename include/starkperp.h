@@ -864,6 +864,40 @@ int sp_fri_check_queries_dev(unsigned log_m, unsigned n_layers, const uint64_t* 
                              size_t n_queries, const uint64_t* index, const uint64_t* pairs,
                              const uint64_t* final_layer, uint8_t* status, void* stream);
 
+/* sp_builtins_eval_points_dev: the composition value of a stark.prove_builtins proof at n_points LDE positions - the
+ *   sum mod p over the present segments (`segments`: SP_SEG_* bits, 1 .. 7) of each segment's composition, bit for
+ *   bit what the prover builds at index pos[i] with sp_air_eval_dev (pedersen), sp_air_eval_ecdsa_dev,
+ *   sp_air_eval_rc16_dev and sp_felt_add_dev.  Same conventions as the two calls above: DEVICE arrays of packed
+ *   felts, HOST challenges, ONE launch on `stream` for any count up to 2^30 (64 points per block, one wave per
+ *   present segment; bracketed by sp_profile_begin / sp_profile_end with units = points), no table that grows with
+ *   the trace: the rc16 part derives the coset point x = shift w_M^pos[i] and the two boundary denominators'
+ *   inverses itself, where the dense call reads three tables of M felts.
+ *     log_n        at least the largest minimum of the present segments (pedersen 9, ecdsa 10, rc16 3); at most 30,
+ *                  24 with rc16 (the dense rc16 call's bound)
+ *     per_*        the segment's stark.periodic_lde table (6 x 2048, 12 x 4096, 2 x 32 felts); NULL when absent
+ *     alphas_host  11 + 26 + 8 felts of the present segments, in that order;  shift_host: the dense calls' rule
+ *     z_host, rc_min, rc_max   the rc16 challenge and limb range (rc_min <= rc_max <= 0xffff, z below p); read
+ *                  only with rc16, z_host may be NULL without it
+ *     pos[i]       LDE index below M = 4 * 2^log_n (u64)
+ *     cur, nxt     n_points x n_cols felts, row-major, n_cols = 4 + 10 + 3 of the present segments: the phase-1 row
+ *                  at pos[i] and the one at (pos[i] + 4) mod M
+ *     pcur, pnxt   n_points felts each: the phase-2 column at those two rows; NULL without rc16
+ *     out[i]       the value;  status[i] = SP_POINT_OK, or SP_POINT_OUT_OF_RANGE with out[i] = 0 when pos[i] >= M or
+ *                  one of the 2 n_cols felts - with rc16 also pcur[i], pnxt[i] - is not below p (nothing is read
+ *                  out of bounds for any pos[i])
+ *   SP_ERR_BAD_ARGUMENT before anything is launched or written: segments outside 1 .. 7, log_n out of range, a bad
+ *   limb range or z with rc16, more than 2^30 points, a needed NULL pointer with n_points > 0, a bad shift.  A count
+ *   of 0 is SP_OK without a launch.  The verifier around it is starkperp.stark.verify_builtins. */
+#define SP_SEG_PEDERSEN 1
+#define SP_SEG_ECDSA 2
+#define SP_SEG_RC16 4
+int sp_builtins_eval_points_dev(unsigned segments, unsigned log_n, const uint64_t* per_pedersen,
+                                const uint64_t* per_ecdsa, const uint64_t* per_rc16, const uint64_t* alphas_host,
+                                const uint64_t* shift_host, const uint64_t* z_host, uint64_t rc_min, uint64_t rc_max,
+                                size_t n_points, const uint64_t* pos, const uint64_t* cur, const uint64_t* nxt,
+                                const uint64_t* pcur, const uint64_t* pnxt, uint64_t* out, uint8_t* status,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -700,14 +700,14 @@ def verify(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]
     air, an n that is no power of two of at least the AIR's period, a shift that is 0 or puts the coset onto the
     trace domain - returns (False, "malformed") before the library is initialised: nothing raises and no such value
     reaches the device.  A prove_builtins proof (air == "builtins") raises ValueError: its verifier needs the
-    second-phase column and the challenge z and is a follow-up; oracle/stark_ref.verify_builtins_proof checks it.
+    second-phase column and the challenge z and is a function of its own, verify_builtins.
 
     The caveat of prove_trace holds here too: this verifies a benchmark-grade argument, NOT a sound proof system -
     no boundary constraint binds the public inputs (they are only absorbed, and range-checked as the oracle does),
     and Q queries at blowup 4 give about 2 Q bits."""
     if isinstance(proof, dict) and proof.get("air") == "builtins":
-        raise ValueError("stark.verify does not take prove_builtins proofs yet (the builtins verifier is a follow-up; "
-                         "oracle/stark_ref.verify_builtins_proof checks them)")
+        raise ValueError("stark.verify does not take prove_builtins proofs (the builtins verifier is "
+                         "stark.verify_builtins)")
     try:
         if not (_wellformed(proof) and _is_int(final_log) and 0 <= final_log <= 30):
             return False, "malformed"
@@ -866,7 +866,7 @@ def prove_builtins(hash_inputs=None, signatures=None, rc_values=None, n_queries:
     their instances (unused builtin cells).  Two committed phases: the builtin columns, then - after the
     challenge z - the permutation product of the range-check segment.  Benchmark-grade like prove_trace (no
     boundary constraint ties the instances to the public inputs except rc_min / rc_max; ~2 bits per query).
-    Verifier: oracle/stark_ref.verify_builtins_proof."""
+    Verifier: verify_builtins (on the GPU; its oracle is oracle/stark_ref.verify_builtins_proof)."""
     return _query_builtins(_commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift, log_rows),
                            n_queries)
 
@@ -1004,3 +1004,314 @@ def _query_builtins(c, n_queries, opener=None):
             entry["layers"].append(pair)
         queries.append(entry)
     return dict(c["head"], queries=queries)
+
+
+# ---- the verifier of prove_builtins proofs ----------------------------------------------------------------------
+# Product twin of oracle/stark_ref.verify_builtins_proof: the same checks in the same order with the same reasons.
+# Host: the transcript and the integer comparisons.  Device: every hash (check_builtins_openings, two calls), the
+# 2 Q composition values over all segments (ONE sp_builtins_eval_points_dev launch, csrc/verify_builtins.hip), the
+# Q n_layers fold steps (ONE sp_fri_check_queries_dev launch), the final layer's coefficients (ntt).
+SEG_BITS = {"pedersen": 1, "ecdsa": 2, "rc16": 4}  # SP_SEG_* of include/starkperp.h
+
+
+def builtins_eval_points(segments, n, pers, alphas, shift, z, rc_min, rc_max, pos, cur, nxt, pcur=None, pnxt=None):
+    """The composition value of a combined builtin trace at arbitrary LDE positions from opened rows
+    (sp_builtins_eval_points_dev): `segments` the list of names as in a proof, `pers` a dict from name to its
+    periodic_lde table, `alphas` the 11 + 26 + 8 of the present segments in that order, pos [k] int64 tensor of LDE
+    indices, cur / nxt [k, n_cols, 4] the phase-1 rows at pos and at (pos + 4) mod 4n, pcur / pnxt [k, 4] the
+    phase-2 column at those rows (with rc16 only; z, rc_min, rc_max are read only then).  Returns (out [k, 4],
+    status [k] uint8): what _commit_builtins builds at those indices, and POINT_OK / POINT_OUT_OF_RANGE per point."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    segments = list(segments)
+    assert segments and segments == [s for s in BUILTIN_SEGMENTS if s in segments]
+    n_cols = sum(AIRS[s]["n_cols"] for s in segments)
+    k = pos.shape[0]
+    assert len(alphas) == sum(AIRS[s]["n_constraints"] for s in segments)
+    assert tuple(cur.shape) == tuple(nxt.shape) == (k, n_cols, 4)
+    assert pos.dtype == torch.int64 and pos.is_contiguous() and cur.is_contiguous() and nxt.is_contiguous()
+    has_rc = "rc16" in segments
+    if has_rc:
+        assert tuple(pcur.shape) == tuple(pnxt.shape) == (k, 4) and pcur.is_contiguous() and pnxt.is_contiguous()
+    tables = [pers[s].data_ptr() if s in segments else None for s in BUILTIN_SEGMENTS]
+    out = torch.empty((k, 4), dtype=torch.int64, device=cur.device)
+    status = torch.empty((k,), dtype=torch.uint8, device=cur.device)
+    _lib.check(lib.sp_builtins_eval_points_dev(
+        sum(SEG_BITS[s] for s in segments), n.bit_length() - 1, tables[0], tables[1], tables[2], pack_felts(alphas),
+        pack_felts([shift]), pack_felts([z]) if has_rc else None, rc_min if has_rc else 0, rc_max if has_rc else 0, k,
+        pos.data_ptr(), cur.data_ptr(), nxt.data_ptr(), pcur.data_ptr() if has_rc else None,
+        pnxt.data_ptr() if has_rc else None, out.data_ptr(), status.data_ptr(), _stream()),
+        "sp_builtins_eval_points_dev")
+    return out, status
+
+
+def check_builtins_openings(proof) -> List[Tuple[str, bool]]:
+    """check_merkle_openings for a prove_builtins proof: one (label, ok) per opening in proof order - per query the
+    four phase-1 rows, each followed by its phase-2 value when the proof has a second phase, then the layer pairs -
+    labelled "q3/phase1/row 517" (against phase1_root), "q3/phase2/row 517" (against phase2_root; the leaf is the
+    value itself, the table has one column) and "q3/layer 2/pos 40" (against layer_roots[2]).  The same two library
+    calls: one ragged chain call hashes the leaves of the phase-1 rows, ONE sp_merkle_verify_paths call with offsets
+    and per-item expected roots checks every path.  A value outside [0, p) makes its opening False; so does a
+    phase-1 row without values.  The Merkle part ONLY: the rest is verify_builtins's."""
+    import numpy as np
+    from . import batch_np
+    P = FIELD_PRIME
+    felt = lambda v: v if 0 <= v < 2**256 else P  # unrepresentable: p itself, which the device flags as out of range
+    two = proof.get("phase2_root") is not None
+    labels, keys, expected, paths, leaves = [], [], [], [], []
+    rows, row_slot, empty = [], [], []  # the chains of the phase-1 rows and the openings they belong to
+
+    def add(label, key, root, path, leaf):
+        labels.append(label)
+        keys.append(key)
+        expected.append(root)
+        paths.append([felt(v) for v in path])
+        leaves.append(leaf)
+
+    for qi, q in enumerate(proof["queries"]):
+        phase2 = iter(q["phase2"]) if two else None
+        for t in q["phase1"]:
+            row_slot.append(len(labels))
+            empty.append(len(t["values"]) == 0)
+            rows.append([felt(v) for v in t["values"]] or [0])
+            add("q%d/phase1/row %d" % (qi, t["row"]), t["row"], proof["phase1_root"], t["path"], 0)
+            t2 = next(phase2, None) if two else None
+            if t2 is not None:
+                add("q%d/phase2/row %d" % (qi, t2["row"]), t2["row"], proof["phase2_root"], t2["path"], felt(t2["value"]))
+        for t2 in phase2 or ():  # more phase-2 openings than phase-1 rows: still in proof order
+            add("q%d/phase2/row %d" % (qi, t2["row"]), t2["row"], proof["phase2_root"], t2["path"], felt(t2["value"]))
+        for k, pair in enumerate(q["layers"]):
+            for o in pair:
+                add("q%d/layer %d/pos %d" % (qi, k, o["pos"]), o["pos"], proof["layer_roots"][k], o["path"], felt(o["value"]))
+    n = len(labels)
+    if n == 0:
+        return []
+    leaf_arr = batch_np.felts_from_ints(leaves)
+    leaf_bad = np.zeros(n, dtype=bool)
+    if rows:
+        row_off = np.zeros(len(rows) + 1, dtype=np.uint32)
+        row_off[1:] = np.cumsum([len(r) for r in rows])
+        hashed, row_st = batch_np.pedersen_chains_ragged(batch_np.felts_from_ints([v for r in rows for v in r]), row_off)
+        slots = np.array(row_slot)
+        bad = (row_st != 0) | np.array(empty)
+        leaf_arr[slots] = hashed
+        leaf_bad[slots] = bad
+        leaf_arr[slots[bad]] = 0  # what a failed chain leaves is unspecified; the opening is False anyway
+    # a position that does not fit its path's height cannot be opened by it
+    fits = np.array([len(p) <= 64 and 0 <= k < (1 << len(p)) for k, p in zip(keys, paths)])
+    off = np.zeros(n + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(p) if f else 0 for p, f in zip(paths, fits)])
+    flat = [v for p, f in zip(paths, fits) if f for v in p]
+    sib = batch_np.felts_from_ints(flat) if flat else np.zeros((0, 4), dtype=np.uint64)
+    key_arr = np.array([k if f else 0 for k, f in zip(keys, fits)], dtype=np.uint64)
+    verdict, _ = batch_np.merkle_verify_paths(leaf_arr, sib, key_arr, batch_np.felts_from_ints([felt(v) for v in expected]),
+                                              offsets=off)
+    ok = verdict & fits & ~leaf_bad
+    return list(zip(labels, [bool(v) for v in ok]))
+
+
+def _wellformed_builtins(proof):
+    """_wellformed for a prove_builtins proof: the keys and types, every felt in [0, p), every integer an int, every
+    path of its tree's height.  What the oracle answers with a reason - the segment list's contents, the public
+    inputs' values, the lengths of layer_roots and final_layer, the number of values of a phase-1 row - is left to
+    verify_builtins."""
+    if not isinstance(proof, dict) or proof.get("air", "builtins") != "builtins":
+        return False
+    segments, n, shift = proof.get("segments"), proof.get("n"), proof.get("shift")
+    if not (isinstance(segments, (list, tuple)) and all(isinstance(s, str) for s in segments)):
+        return False
+    has_rc = "rc16" in segments
+    # 2^24 rows is the bound of the dense rc16 composition: no prover made a longer proof with that segment
+    if not (_is_int(n) and 1 <= n <= 1 << (24 if has_rc else 30) and n & (n - 1) == 0):
+        return False
+    if not (_is_felt(shift) and shift != 0 and pow(shift, 4 * n, FIELD_PRIME) != 1):
+        return False
+    if not (_is_int(proof.get("seed")) and 0 <= proof["seed"] < 1 << 256 and _is_felt(proof.get("phase1_root"))):
+        return False
+    if has_rc and not _is_felt(proof.get("phase2_root")):
+        return False
+    pub = proof.get("public_inputs")
+    if not isinstance(pub, dict):
+        return False
+    if has_rc and not (_is_int(pub.get("rc_min")) and _is_int(pub.get("rc_max"))):
+        return False
+    if "ecdsa" in segments:
+        sigs = pub.get("signatures")
+        if not (isinstance(sigs, (list, tuple)) and all(
+                isinstance(sig, (list, tuple)) and len(sig) == 5 and all(_is_int(v) and 0 <= v < 1 << 256 for v in sig)
+                for sig in sigs)):
+            return False
+    if not (_felt_list(proof.get("layer_roots")) and _felt_list(proof.get("final_layer"))):
+        return False
+    queries = proof.get("queries")
+    if not isinstance(queries, (list, tuple)):
+        return False
+    log_m = n.bit_length() + 1
+    for q in queries:
+        if not (isinstance(q, dict) and _is_int(q.get("index")) and isinstance(q.get("phase1"), (list, tuple))
+                and isinstance(q.get("phase2"), (list, tuple)) and isinstance(q.get("layers"), (list, tuple))
+                and len(q["phase1"]) == 4 and (len(q["phase2"]) == 4 or not has_rc)):
+            return False
+        for t in q["phase1"]:
+            if not (isinstance(t, dict) and _is_int(t.get("row")) and _felt_list(t.get("values"))
+                    and _felt_list(t.get("path"), log_m)):
+                return False
+        for t in q["phase2"] if has_rc else ():  # without rc16 nothing reads the second phase
+            if not (isinstance(t, dict) and _is_int(t.get("row")) and _is_felt(t.get("value"))
+                    and _felt_list(t.get("path"), log_m)):
+                return False
+        for k, pair in enumerate(q["layers"]):
+            if not (isinstance(pair, (list, tuple)) and len(pair) == 2):
+                return False
+            for o in pair:
+                if not (isinstance(o, dict) and _is_int(o.get("pos")) and _is_felt(o.get("value"))
+                        and _felt_list(o.get("path"), max(log_m - k, 0))):
+                    return False
+    return True
+
+
+def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]:
+    """Verifier of prove_builtins proofs: returns (ok, reason) with the reasons of
+    oracle/stark_ref.verify_builtins_proof, the first failure in that function's order - "segments", "public inputs"
+    (the rc16 limb range, the signatures' side conditions, n against each segment's period), "shape" (also fewer
+    than one layer, and a given `n_queries` that is not the number of queries), "final layer degree", then per query
+    "query index", "opened rows", "phase 1 path", "phase 2 path", "composition value" and per layer "layer
+    positions", "layer path", "fold consistency at layer k" - or (True, "ok").  `final_log` is the prover's.
+
+    Where it runs: the SHA-256 transcript - the flattened public inputs exactly as the prover absorbs them, then
+    phase1_root, the challenge rc16_z, phase2_root, the alphas, the betas, the query indices - and the comparisons of
+    indices, rows and positions on the host; every hash on the GPU through check_builtins_openings (two calls); the
+    composition value of the 2 Q opened points, summed over the segments, in ONE sp_builtins_eval_points_dev launch
+    and the Q n_layers fold steps in ONE sp_fri_check_queries_dev launch; the final layer's coefficients through
+    ntt.  Everything is computed, then the first failure is reported.  A phase-1 row with the wrong number of values
+    is "opened rows" at that row's turn; the composition launch covers the queries before the first such query.
+    Without rc16 there is no second phase: phase2 is empty, phase2_root None and z = 0.
+
+    A malformed proof - a missing key, a non-integer, a felt outside [0, p), a path of the wrong length, `segments`
+    not a list of strings, `public_inputs` not the dict the segments need, an n that is no power of two, a shift
+    that is 0 or puts the coset onto the trace domain - returns (False, "malformed") before the library is
+    initialised: nothing raises and no such value reaches the device.
+
+    The caveat of prove_trace holds here too: this verifies a benchmark-grade argument, NOT a sound proof system -
+    no boundary constraint binds the instances to the public inputs except rc_min / rc_max (the rest is only
+    absorbed, and checked as the oracle does), and Q queries at blowup 4 give about 2 Q bits."""
+    try:
+        if not (_wellformed_builtins(proof) and _is_int(final_log) and 0 <= final_log <= 30):
+            return False, "malformed"
+    except Exception:  # an object that misbehaves when inspected is malformed too
+        return False, "malformed"
+    n, seed, shift, segments = proof["n"], proof["seed"], proof["shift"], list(proof["segments"])
+    if not segments or segments != [s for s in BUILTIN_SEGMENTS if s in segments]:
+        return False, "segments"
+    n_cols = sum(AIRS[s]["n_cols"] for s in segments)
+    n_alphas = sum(AIRS[s]["n_constraints"] for s in segments)
+    has_rc = "rc16" in segments
+    pub = proof["public_inputs"]
+    rc_min = rc_max = 0
+    if has_rc:
+        rc_min, rc_max = pub["rc_min"], pub["rc_max"]
+        if not 0 <= rc_min <= rc_max < 1 << 16 or n % RC16_LIMBS:
+            return False, "public inputs"
+    if "ecdsa" in segments:
+        sigs = pub["signatures"]
+        if n % 1024 or len(sigs) != n // 1024 or not _public_inputs_ok("ecdsa", n, [v for sig in sigs for v in sig]):
+            return False, "public inputs"
+    if "pedersen" in segments and n % 512:
+        return False, "public inputs"
+    m = n << BLOWUP_LOG
+    log_m = m.bit_length() - 1
+    roots, final, queries = proof["layer_roots"], proof["final_layer"], proof["queries"]
+    n_layers = log_m - final_log
+    if len(roots) != n_layers or len(final) != 1 << final_log or n_layers < 1:
+        return False, "shape"
+    if n_queries is not None and n_queries != len(queries):
+        return False, "shape"
+    if any(len(q["layers"]) != n_layers for q in queries):
+        return False, "malformed"
+    flat_pub = [len(segments)] + [BUILTIN_SEGMENTS.index(s) for s in segments]
+    if has_rc:
+        flat_pub += [rc_min, rc_max]
+    if "ecdsa" in segments:
+        flat_pub += [v for sig in pub["signatures"] for v in sig]
+    tr = Transcript("builtins", n, shift, seed, flat_pub)
+    tr.absorb("phase1_root", proof["phase1_root"])
+    z = 0
+    if has_rc:
+        z = tr.challenge("rc16_z")
+        tr.absorb("phase2_root", proof["phase2_root"])
+    alphas = [tr.challenge("alpha", k) for k in range(n_alphas)]
+    betas = []
+    for k in range(n_layers):
+        tr.absorb("layer_root", roots[k])
+        betas.append(tr.challenge("beta", k + 1))
+    tr.absorb("final_layer", *final)
+    indices = [tr.challenge("query", qi, modulus=m // 2) for qi in range(len(queries))]
+    torch = _torch()
+    final_t = felts_to_tensor(final)
+    coeffs = tensor_to_felts(ntt(final_t, inverse=True))  # the zero pattern of the interpolant's, as in verify
+    if any(c != 0 for c in coeffs[3 * n >> n_layers:]):
+        return False, "final layer degree"
+    if not queries:
+        return True, "ok"
+    openings = iter(check_builtins_openings(dict(proof, phase2_root=proof["phase2_root"] if has_rc else None)))
+    dev = final_t.device
+    # the composition launch stops before the first query with an ill-shaped phase-1 row: the answer is "opened
+    # rows" at that row's turn at the latest
+    shaped = 0
+    while shaped < len(queries) and all(len(t["values"]) == n_cols for t in queries[shaped]["phase1"]):
+        shaped += 1
+    comp, comp_st = [], []
+    if shaped:
+        head = queries[:shaped]
+        pers = {s: periodic_lde(n, shift, dev, s) for s in segments}
+        positions = [pos for j in indices[:shaped] for pos in (j, j + m // 2)]
+        cur = felts_to_tensor([v for q in head for side in (0, 1) for v in q["phase1"][2 * side]["values"]], dev)
+        nxt = felts_to_tensor([v for q in head for side in (0, 1) for v in q["phase1"][2 * side + 1]["values"]], dev)
+        pcur = pnxt = None
+        if has_rc:
+            pcur = felts_to_tensor([q["phase2"][2 * side]["value"] for q in head for side in (0, 1)], dev)
+            pnxt = felts_to_tensor([q["phase2"][2 * side + 1]["value"] for q in head for side in (0, 1)], dev)
+        shape = (len(positions), n_cols, 4)
+        comp, comp_st = builtins_eval_points(segments, n, pers, alphas, shift, z, rc_min, rc_max,
+                                             torch.tensor(positions, dtype=torch.int64, device=dev),
+                                             cur.reshape(shape), nxt.reshape(shape), pcur, pnxt)
+    pairs = felts_to_tensor([o["value"] for q in queries for pair in q["layers"] for o in pair], dev)
+    fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
+                                pairs.reshape(len(queries), n_layers, 2, 4), final_t)
+    if shaped:
+        comp, comp_st = tensor_to_felts(comp), comp_st.cpu().tolist()
+    fold_st = fold_st.cpu().tolist()
+    for qi, (q, j) in enumerate(zip(queries, indices)):
+        phase1_ok, phase2_ok = [], []
+        for _ in range(4):
+            phase1_ok.append(next(openings)[1])
+            if has_rc:
+                phase2_ok.append(next(openings)[1])
+        layer_ok = [[next(openings)[1] for _ in range(2)] for _ in range(n_layers)]
+        if q["index"] != j:
+            return False, "query index"
+        want_rows = [j, (j + 4) % m, j + m // 2, (j + m // 2 + 4) % m]
+        if [t["row"] for t in q["phase1"]] != want_rows or (has_rc and [t["row"] for t in q["phase2"]] != want_rows):
+            return False, "opened rows"
+        for t, ok in zip(q["phase1"], phase1_ok):
+            if len(t["values"]) != n_cols:
+                return False, "opened rows"
+            if not ok:
+                return False, "phase 1 path"
+        if not all(phase2_ok):
+            return False, "phase 2 path"
+        for side in (0, 1):
+            if comp_st[2 * qi + side] != POINT_OK or q["layers"][0][side]["value"] != comp[2 * qi + side]:
+                return False, "composition value"
+        jk, mk = j, m
+        for k in range(n_layers):
+            jk %= mk // 2
+            a, b = q["layers"][k]
+            if (a["pos"], b["pos"]) != (jk, jk + mk // 2):
+                return False, "layer positions"
+            if not all(layer_ok[k]):
+                return False, "layer path"
+            if fold_st[qi][k] != FOLD_OK:
+                return False, "fold consistency at layer %d" % k
+            mk //= 2
+    return True, "ok"
