@@ -21,18 +21,15 @@
  *     call's buffers must stay valid until the work enqueued on its stream has completed.
  *   - Threading: every entry point may be called from any host thread.  One recursive lock
  *     serialises the host-side bookkeeping; scratch, window tables of the verifier and NTT work
- *     columns are per stream, so _dev calls on different streams overlap on the device.  The
- *     host-pointer batches that carry no shared state - sp_pedersen_batch, sp_pedersen_chains,
- *     sp_pedersen_chains_ragged, sp_merkle_fold_paths, sp_merkle_verify_paths, sp_merkle_verify_update,
- *     sp_ecdsa_verify_batch (per-signature ladder), sp_ecdsa_sign_batch, sp_ecdsa_sign_rfc6979_batch,
- *     sp_public_key_batch, sp_felt_sqrt_batch, sp_stark_key_y_batch, sp_ec_mult_batch, sp_ec_lincomb_batch,
- *     sp_ec_add_batch -
- *     run on one of 16 host lanes (own stream, own staging buffer) and hold the lock only while a
- *     kernel is enqueued: calls from different threads overlap on the device - on the devices, after
- *     sp_init_devices - (a seventeenth concurrent caller waits for a lane).  Keyed verification runs on a lane too and holds the
- *     lock to register keys and to enqueue; a persistent tree has its own stream and mutex (below).  The remaining
- *     host-pointer calls (the scalar chain calls, sp_merkle_root / _sparse_root, key registration) hold the lock for
- *     their whole staged round trip.
+ *     columns are per stream, so _dev calls on different streams overlap on the device.  Every
+ *     host-pointer batch runs on one of 16 host lanes (own stream, own staging buffers), makes one round trip on
+ *     that stream - no device-wide wait - and holds the lock only while it enqueues: calls from different threads
+ *     overlap on the device - on the devices, after sp_init_devices - (a seventeenth concurrent caller waits for a
+ *     lane).  Keyed verification holds the lock to register keys and to enqueue; a persistent tree has its own
+ *     stream and mutex (below).  The exceptions, which hold the lock from start to end: key registration
+ *     (sp_ecdsa_register_keys), sp_ecdsa_key_cache_reset, sp_init and sp_init_devices.
+ *     A lane's device buffer only grows until sp_shutdown: one huge sp_merkle_root or sp_pedersen_batch leaves its
+ *     buffer parked on the lane that served it.
  *     Each entry point binds the device given to sp_init for its duration and restores the calling
  *     thread's current HIP device on return.
  */
@@ -531,7 +528,8 @@ int sp_ecdsa_key_cache_reset(void);
  *                      (it depends on k's HMAC chain, not on d); the exceptional-case branches of the attempt
  *                      (r = 0, out-of-range w: 2^-55 events) are data dependent;
  *   at rest            nonces and HMAC states of the compacted pipeline are scrubbed on the stream behind their
- *                      last reader, staged private keys of the host-pointer calls likewise; r, s and the public
+ *                      last reader, staged private keys and nonces of the host-pointer calls likewise, and their
+ *                      copy in the lane's page-locked block is zeroed before the call returns; r, s and the public
  *                      key are public.  Buffers the CALLER owns (d in the _dev calls) are the caller's to scrub.
  * The reference is no different in kind: signature.py:137-173 signs with Python big integers, a recursive
  * double-and-add ec_mult whose branches follow the bits of k (math_utils.py:91-100) and sympy's variable-time

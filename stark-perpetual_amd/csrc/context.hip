@@ -580,8 +580,6 @@ static void free_tables(Context& c) {
   if (c.d_plan) (void)hipFree(c.d_plan);
   c.ped = c.gen = c.gen_masked = nullptr;
   c.d_plan = nullptr;
-  c.io.release();
-  c.io2.release();
   c.ready = false;
 }
 

@@ -68,15 +68,14 @@ struct PinnedBuffer {
   size_t bytes = 0;
   hipError_t reserve(size_t need) {  // grow-only; contents are not preserved
     if (need <= bytes) return hipSuccess;
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = nullptr;
-    bytes = 0;
+    release();
     size_t want = need + need / 4;
     hipError_t e = hipHostMalloc(&ptr, want, hipHostMallocDefault);
     if (e == hipSuccess) bytes = want;
     return e;
   }
-  void release() {
+  void release() {  // wiped first: a signer's private keys and nonces may have crossed it (StagedTrip::secret)
+    if (ptr) explicit_bzero(ptr, bytes);
     if (ptr) (void)hipHostFree(ptr);
     ptr = nullptr;
     bytes = 0;
@@ -96,16 +95,26 @@ struct Piece {
 //   stage == nullptr   DIRECT: one copy per piece, from / into the caller's arrays (a batch above PINNED_STAGE_MAX, or
 //                      a page-locked allocation that failed - its error is cleared here).
 // up() before the kernels, down() behind them, finish() after the caller's own wait on the stream.  A call whose copies
-// have another shape (tree_enqueue, the large page of sp_tree_scan, ecdsa.hip stage_in_lane) reads `stage` and copies
-// for itself.
+// have another shape (tree_enqueue, the large page of sp_tree_scan) reads `stage` and copies for itself.
+// secret(at, bytes) before up() marks a range of the inputs as private keys or nonces: the block's copy of it is zeroed
+// by finish() and, on a path that never gets there, by the destructor (include/starkperp.h "threat model": at rest).
 struct StagedTrip {
   char* stage = nullptr;
   hipStream_t st;
   size_t up_bytes = 0;  // where the outputs start in the block
+  size_t secret_at = 0, secret_bytes = 0;
   static bool fits(size_t bytes) { return bytes <= PINNED_STAGE_MAX; }
   StagedTrip(PinnedBuffer& buf, size_t bytes, hipStream_t stream) : st(stream) {
     if (fits(bytes) && buf.reserve(bytes) == hipSuccess) stage = (char*)buf.ptr;
     else (void)hipGetLastError();
+  }
+  ~StagedTrip() { wipe(); }
+  StagedTrip(const StagedTrip&) = delete;
+  StagedTrip& operator=(const StagedTrip&) = delete;
+  void secret(size_t at, size_t bytes) { secret_at = at; secret_bytes = bytes; }
+  void wipe() {  // explicit_bzero: a store the compiler may not drop
+    if (stage && secret_bytes) explicit_bzero(stage + secret_at, secret_bytes);
+    secret_bytes = 0;
   }
   // the host pieces -> dev, one behind the other
   hipError_t up(void* dev, std::initializer_list<Piece> pieces) {
@@ -133,13 +142,14 @@ struct StagedTrip {
     }
     return stage ? hipMemcpyAsync(stage + up_bytes, dev, at, hipMemcpyDeviceToHost, st) : hipSuccess;
   }
-  // after the wait: the block -> the host pieces (direct: they are there already)
-  void finish(std::initializer_list<Piece> pieces) const {
+  // after the wait: the block -> the host pieces (direct: they are there already); the secret inputs leave the block
+  void finish(std::initializer_list<Piece> pieces) {
     size_t at = up_bytes;
     for (const Piece& p : pieces) {
       if (p.ptr && stage) std::memcpy(p.ptr, stage + at, p.bytes);
       at += p.bytes;
     }
+    wipe();
   }
 };
 
@@ -201,11 +211,8 @@ struct Context {
   PedPlan plan;                // host copy
   PedPlan* d_plan = nullptr;   // device copy the kernels read (uniform loads)
   size_t table_bytes = 0;
-  DeviceBuffer io;             // staging for host-pointer entry points
-  DeviceBuffer io2;
   uint64_t host_calls = 0;     // host-lane calls served (sp_context_info)
-  // Recursive: host-pointer entry points hold it across the staging copies AND the nested _dev
-  // call, so two host threads can never interleave on the shared staging buffers.  ONE lock for all
+  // Recursive: an entry point that holds it may call a _dev entry point, which takes it again.  ONE lock for all
   // contexts: it also guards the per-stream scratch maps, which are shared; it is held while work is
   // enqueued, never while the device runs a stateless batch.
   std::recursive_mutex& mu = global_mu();
@@ -242,7 +249,7 @@ constexpr int HOST_LANES = 16;
 struct HostLane {
   hipStream_t stream = nullptr;
   int stream_ctx = -1;          // the context the stream was created for
-  DeviceBuffer io;
+  DeviceBuffer io;              // grow-only until sp_shutdown: one huge batch parks its buffer on its lane
   PinnedBuffer hio;             // host-side staging of small batches (see PinnedBuffer)
   bool busy = false;
 };

@@ -887,52 +887,6 @@ int sp_ecdsa_verify_batch_dev(const uint64_t* z, const uint64_t* r, const uint64
   return SP_OK;
 }
 
-// Host staging helper: copies `count` felt arrays (each n felts; null pointers stay null) to the
-// device staging buffer and returns device pointers.
-static int stage_in(const uint64_t* const* host, int count, size_t n, uint64_t** dev, size_t extra,
-                    char** extra_ptr) {
-  Context& c = ctx();
-  const size_t fb = n * 32;
-  SP_HIP(c.io2.reserve((size_t)count * fb + extra + 256));
-  char* base = (char*)c.io2.ptr;
-  for (int i = 0; i < count; ++i) {
-    if (host[i]) {
-      dev[i] = (uint64_t*)(base + (size_t)i * fb);
-      SP_HIP(hipMemcpy(dev[i], host[i], fb, hipMemcpyHostToDevice));
-    } else {
-      dev[i] = nullptr;
-    }
-  }
-  *extra_ptr = base + (size_t)count * fb;
-  return SP_OK;
-}
-
-// The same on a host lane (context.hpp): the lane's own staging buffer, copies ordered on the lane's stream.
-static int stage_in_lane(HostLane& L, const uint64_t* const* host, int count, size_t n, uint64_t** dev, size_t extra,
-                         char** extra_ptr) {
-  const size_t fb = n * 32;
-  SP_HIP(L.io.reserve((size_t)count * fb + extra + 256));
-  char* base = (char*)L.io.ptr;
-  // small batches go through the lane's page-locked buffer (one host memcpy per input, then asynchronous DMA); a
-  // failed page-locked allocation just keeps the direct copies
-  char* const stage = StagedTrip(L.hio, (size_t)count * fb, L.stream).stage;
-  for (int i = 0; i < count; ++i) {
-    if (host[i]) {
-      dev[i] = (uint64_t*)(base + (size_t)i * fb);
-      const void* src = host[i];
-      if (stage) {
-        std::memcpy(stage + (size_t)i * fb, host[i], fb);
-        src = stage + (size_t)i * fb;
-      }
-      SP_HIP(hipMemcpyAsync(dev[i], src, fb, hipMemcpyHostToDevice, L.stream));
-    } else {
-      dev[i] = nullptr;
-    }
-  }
-  *extra_ptr = base + (size_t)count * fb;
-  return SP_OK;
-}
-
 static int key_sentinels() {
   const uint8_t f[2] = {KEY_INVALID_X, KEY_OFF_CURVE};
   SP_HIP(hipMemcpy(g_keys.flag.ptr, f, 2, hipMemcpyHostToDevice));
@@ -1275,11 +1229,15 @@ static int verify_batch_keyed_impl(const uint64_t* z, const uint64_t* r, const u
   // and three copies from pageable memory are the longest part of this function's host time (0.5 ms for 4096
   // signatures, profiles/r06_c3_timeline.txt) - round 5 made them under the lock, where sp_order_batch's tree update
   // (the critical path of that call) queued behind them.
-  const uint64_t* host[3] = {z, r, s};
-  uint64_t* dev[3];
-  char* extra;
-  int rc = stage_in_lane(L, host, 3, n, dev, n * 4 + n, &extra);
-  if (rc != SP_OK) return rc;
+  // device: z | r | s | slot handles | verdict bytes
+  const size_t fb = n * 32;
+  SP_HIP(L.io.reserve(3 * fb + n * 4 + n + 256));
+  uint64_t* dz = (uint64_t*)L.io.ptr;
+  uint32_t* d_slots = (uint32_t*)(dz + 12 * n);
+  d_res = (uint8_t*)(d_slots + n);
+  StagedTrip trip(L.hio, 3 * fb + n, L.stream);
+  SP_HIP(trip.up(dz, {{z, fb}, {r, fb}, {s, fb}}));
+  int rc;
   tl_mark("keyed verify: inputs staged");
   // sp_order_batch parks its verifier here until the tree update - the critical path of that call - has enqueued its
   // levels: both need the library lock, and the verifier used to win the race every few calls (+ 0.35 ms)
@@ -1298,18 +1256,17 @@ static int verify_batch_keyed_impl(const uint64_t* z, const uint64_t* r, const u
     if (policy && rc == SP_ERR_CACHE_FULL) { *fell_back = true; lane_drain(&L); return SP_OK; }  // still no room: the ladder
     if (rc != SP_OK) { lane_drain(&L); return rc; }
     tl_mark("keyed verify: keys registered");
-    uint32_t* d_slots = (uint32_t*)extra;
-    d_res = (uint8_t*)(extra + n * 4);
     SP_HIP(hipMemcpyAsync(d_slots, slots.data(), n * 4, hipMemcpyHostToDevice, L.stream));
-    rc = sp_ecdsa_verify_keyed_dev(dev[0], dev[1], dev[2], d_slots, d_res, n, L.stream);
+    rc = sp_ecdsa_verify_keyed_dev(dz, dz + 4 * n, dz + 8 * n, d_slots, d_res, n, L.stream);
     if (rc != SP_OK) return rc;
     tl_mark("keyed verify: enqueued");
   }
   // The verdicts come back OUTSIDE the lock: a copy into the caller's pageable memory makes the runtime wait for the
   // kernel in front of it, and round 5 held the library lock through that wait (the whole verification kernel,
   // 0.25 - 0.5 ms for 4096 signatures) - whoever needed the lock next, sp_order_batch's tree update for one, queued.
-  SP_HIP(hipMemcpyAsync(result, d_res, n, hipMemcpyDeviceToHost, L.stream));
+  SP_HIP(trip.down(d_res, {{result, n}}));
   SP_HIP(hipStreamSynchronize(L.stream));  // `slots` stays alive until the copy that reads it has run
+  trip.finish({{result, n}});
   return SP_OK;
 }
 
@@ -1361,15 +1318,18 @@ int sp_ecdsa_verify_batch(const uint64_t* z, const uint64_t* r, const uint64_t* 
   SP_REQUIRE_READY();
   if (ls.open() != SP_OK) return SP_ERR_HIP;
   HostLane& L = *ls.lane;
-  const uint64_t* host[5] = {z, r, s, qx, qy};
-  uint64_t* dev[5];
-  char* extra;
-  int rc = stage_in_lane(L, host, 5, n, dev, n, &extra);
+  // device: z | r | s | qx | qy (x-only keys: no slot) | verdict bytes
+  const size_t fb = n * 32, in_bytes = (qy ? 5 : 4) * fb;
+  SP_HIP(L.io.reserve(in_bytes + n + 256));
+  uint64_t* dz = (uint64_t*)L.io.ptr;
+  uint8_t* d_res = (uint8_t*)L.io.ptr + in_bytes;
+  StagedTrip trip(L.hio, in_bytes + n, L.stream);
+  SP_HIP(trip.up(dz, {{z, fb}, {r, fb}, {s, fb}, {qx, fb}, {qy, qy ? fb : 0}}));
+  int rc = sp_ecdsa_verify_batch_dev(dz, dz + 4 * n, dz + 8 * n, dz + 12 * n, qy ? dz + 16 * n : nullptr, d_res, n, L.stream);
   if (rc != SP_OK) return rc;
-  rc = sp_ecdsa_verify_batch_dev(dev[0], dev[1], dev[2], dev[3], dev[4], (uint8_t*)extra, n, L.stream);
-  if (rc != SP_OK) return rc;
-  SP_HIP(hipMemcpyAsync(result, extra, n, hipMemcpyDeviceToHost, L.stream));
+  SP_HIP(trip.down(d_res, {{result, n}}));
   SP_HIP(hipStreamSynchronize(L.stream));
+  trip.finish({{result, n}});
   return SP_OK;
 }
 
@@ -1493,25 +1453,25 @@ int sp_ecdsa_sign_batch(const uint64_t* z, const uint64_t* d, const uint64_t* k,
   if (ls.open() != SP_OK) return SP_ERR_HIP;
   Context& c = ctx();
   HostLane& L = *ls.lane;
-  const uint64_t* host[3] = {z, d, k};
-  uint64_t* dev[3];
-  char* extra;
+  // device: z | d | k | r | s | status bytes
   const size_t fb = n * 32;
-  int rc = stage_in_lane(L, host, 3, n, dev, 2 * fb + n, &extra);
-  if (rc != SP_OK) return rc;
-  SecretScrub wipe(dev[1], 2 * fb, L.stream);  // the staged private keys and nonces (dev[1], dev[2] are adjacent)
-  uint64_t* dr = (uint64_t*)extra;
-  uint64_t* ds = (uint64_t*)(extra + fb);
-  uint8_t* dst = (uint8_t*)(extra + 2 * fb);
+  SP_HIP(L.io.reserve(5 * fb + n + 256));
+  uint64_t* dz = (uint64_t*)L.io.ptr;
+  uint64_t *dd = dz + 4 * n, *dr = dz + 12 * n, *ds = dz + 16 * n;
+  uint8_t* dst = (uint8_t*)(dz + 20 * n);
+  const std::initializer_list<Piece> outs = {{r, fb}, {s, fb}, {status, n}};
+  StagedTrip trip(L.hio, 5 * fb + n, L.stream);
+  trip.secret(fb, 2 * fb);                // the private keys and the nonces, adjacent: in the page-locked block ...
+  SecretScrub wipe(dd, 2 * fb, L.stream);  // ... and in the lane's buffer; armed before anything is uploaded
+  SP_HIP(trip.up(dz, {{z, fb}, {d, fb}, {k, fb}}));
   SP_HIP(hipMemsetAsync(dr, 0, 2 * fb, L.stream));
-  hipLaunchKernelGGL(ecdsa_sign_kernel, dim3(nblocks(n, 128)), dim3(128), 0, L.stream, dev[0], dev[1], dev[2],
+  hipLaunchKernelGGL(ecdsa_sign_kernel, dim3(nblocks(n, 128)), dim3(128), 0, L.stream, dz, dd, dd + 4 * n,
                      dr, ds, dst, n, c.secret_gen(), c.secret_wbits(), c.secret_nwin());
   SP_HIP(hipGetLastError());
-  SP_HIP(hipMemcpyAsync(r, dr, fb, hipMemcpyDeviceToHost, L.stream));
-  SP_HIP(hipMemcpyAsync(s, ds, fb, hipMemcpyDeviceToHost, L.stream));
-  SP_HIP(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, L.stream));
+  SP_HIP(trip.down(dr, outs));
   SP_HIP(wipe.finish());
   SP_HIP(hipStreamSynchronize(L.stream));
+  trip.finish(outs);
   return SP_OK;
 }
 
@@ -1524,29 +1484,30 @@ int sp_ecdsa_sign_rfc6979_batch(const uint64_t* z, const uint64_t* d, const uint
   if (ls.open() != SP_OK) return SP_ERR_HIP;
   Context& c = ctx();
   HostLane& L = *ls.lane;
-  const uint64_t* host[2] = {z, d};
-  uint64_t* dev[2];
-  char* extra;
-  const size_t fb = n * 32;
-  int rc = stage_in_lane(L, host, 2, n, dev, 2 * fb + n * 8 + n + 64, &extra);
-  if (rc != SP_OK) return rc;
-  SecretScrub wipe(dev[1], fb, L.stream);  // the staged private keys do not stay in the lane's buffer
-  uint64_t* dr = (uint64_t*)extra;
-  uint64_t* ds = (uint64_t*)(extra + fb);
-  uint64_t* dseed = (uint64_t*)(extra + 2 * fb);
-  uint8_t* dst = (uint8_t*)(extra + 2 * fb + n * 8);
+  // device: z | d | seeds, padded to whole felts (none: no slot) | r | s | status bytes
+  const size_t fb = n * 32, seed_bytes = seeds ? n * 8 : 0, seed_pad = (32 - seed_bytes % 32) % 32;
+  const size_t in_bytes = 2 * fb + seed_bytes + seed_pad;
+  SP_HIP(L.io.reserve(in_bytes + 2 * fb + n + 256));
+  uint64_t* dz = (uint64_t*)L.io.ptr;
+  uint64_t *dd = dz + 4 * n, *dseed = dz + 8 * n;
+  uint64_t* dr = (uint64_t*)((char*)L.io.ptr + in_bytes);
+  uint64_t* ds = dr + 4 * n;
+  uint8_t* dst = (uint8_t*)(dr + 8 * n);
+  const std::initializer_list<Piece> outs = {{r, fb}, {s, fb}, {status, n}};
+  StagedTrip trip(L.hio, in_bytes + 2 * fb + n, L.stream);
+  trip.secret(fb, fb);                 // the private keys: in the page-locked block ...
+  SecretScrub wipe(dd, fb, L.stream);  // ... and in the lane's buffer; armed before anything is uploaded
+  SP_HIP(trip.up(dz, {{z, fb}, {d, fb}, {seeds, seed_bytes}, {nullptr, seed_pad}}));
   SP_HIP(hipMemsetAsync(dr, 0, 2 * fb, L.stream));
-  if (seeds) SP_HIP(hipMemcpyAsync(dseed, seeds, n * 8, hipMemcpyHostToDevice, L.stream));
   {
     ctx_lock lk(c.mu);  // the compacted pipeline keeps per-stream scratch in a shared map
-    rc = enqueue_sign_rfc6979(c, dev[0], dev[1], seeds ? dseed : nullptr, dr, ds, dst, n, L.stream);
+    const int rc = enqueue_sign_rfc6979(c, dz, dd, seeds ? dseed : nullptr, dr, ds, dst, n, L.stream);
     if (rc != SP_OK) return rc;
   }
-  SP_HIP(hipMemcpyAsync(r, dr, fb, hipMemcpyDeviceToHost, L.stream));
-  SP_HIP(hipMemcpyAsync(s, ds, fb, hipMemcpyDeviceToHost, L.stream));
-  SP_HIP(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, L.stream));
+  SP_HIP(trip.down(dr, outs));
   SP_HIP(wipe.finish());
   SP_HIP(hipStreamSynchronize(L.stream));
+  trip.finish(outs);
   return SP_OK;
 }
 
@@ -1605,25 +1566,25 @@ int sp_public_key_batch(const uint64_t* d, uint64_t* qx, uint64_t* qy, uint8_t* 
   if (ls.open() != SP_OK) return SP_ERR_HIP;
   Context& c = ctx();
   HostLane& L = *ls.lane;
-  const uint64_t* host[1] = {d};
-  uint64_t* dev[1];
-  char* extra;
+  // device: d | qx | qy | status bytes
   const size_t fb = n * 32;
-  int rc = stage_in_lane(L, host, 1, n, dev, 2 * fb + n, &extra);
-  if (rc != SP_OK) return rc;
-  SecretScrub wipe(dev[0], fb, L.stream);  // the staged private keys do not stay in the lane's buffer
-  uint64_t* dx = (uint64_t*)extra;
-  uint64_t* dy = (uint64_t*)(extra + fb);
-  uint8_t* dst = (uint8_t*)(extra + 2 * fb);
+  SP_HIP(L.io.reserve(3 * fb + n + 256));
+  uint64_t* dd = (uint64_t*)L.io.ptr;
+  uint64_t *dx = dd + 4 * n, *dy = dd + 8 * n;
+  uint8_t* dst = (uint8_t*)(dd + 12 * n);
+  const std::initializer_list<Piece> outs = {{qx, fb}, {qy, fb}, {status, n}};
+  StagedTrip trip(L.hio, 3 * fb + n, L.stream);
+  trip.secret(0, fb);                  // the private keys: in the page-locked block ...
+  SecretScrub wipe(dd, fb, L.stream);  // ... and in the lane's buffer; armed before anything is uploaded
+  SP_HIP(trip.up(dd, {{d, fb}}));
   SP_HIP(hipMemsetAsync(dx, 0, 2 * fb, L.stream));
-  hipLaunchKernelGGL(public_key_kernel, dim3(nblocks(n, 128)), dim3(128), 0, L.stream, dev[0], dx, dy, dst, n,
+  hipLaunchKernelGGL(public_key_kernel, dim3(nblocks(n, 128)), dim3(128), 0, L.stream, dd, dx, dy, dst, n,
                      c.secret_gen(), c.secret_wbits(), c.secret_nwin());
   SP_HIP(hipGetLastError());
-  SP_HIP(hipMemcpyAsync(qx, dx, fb, hipMemcpyDeviceToHost, L.stream));
-  if (qy) SP_HIP(hipMemcpyAsync(qy, dy, fb, hipMemcpyDeviceToHost, L.stream));
-  if (status) SP_HIP(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, L.stream));
+  SP_HIP(trip.down(dx, outs));
   SP_HIP(wipe.finish());
   SP_HIP(hipStreamSynchronize(L.stream));
+  trip.finish(outs);
   return SP_OK;
 }
 

@@ -25,7 +25,6 @@
 
 namespace sp {
 
-static DeviceBuffer g_sparse_buf;
 // empty-subtree roots are a pure function of the empty leaf: cached on the host per leaf value
 static std::map<std::vector<uint64_t>, std::vector<uint64_t>> g_empty_cache;  // leaf -> 65 felts
 // Work buffer of sp_merkle_verify_update[_dev], one per stream like the hash scratch: roots | node indices | child lists
@@ -34,7 +33,6 @@ static std::map<std::vector<uint64_t>, std::vector<uint64_t>> g_empty_cache;  //
 using VerifyWork = RetiringBuffer<char>;
 static std::map<StreamKey, VerifyWork> g_verify_work;
 void release_merkle_state() {
-  g_sparse_buf.release();
   g_empty_cache.clear();
   for (auto& kv : g_verify_work) kv.second.release();
   g_verify_work.clear();
@@ -63,23 +61,24 @@ static bool keys_ok(unsigned height, const uint64_t* keys, size_t n, bool ordere
   return true;
 }
 
-// empty-subtree roots: empties[k+1] = H(empties[k], empties[k]); 64 sequential hashes the first
-// time a given empty leaf is seen, then served from the host-side cache (65 felts per leaf value)
-static int empty_roots(const uint64_t* empty_leaf, const Scratch& s, const std::vector<uint64_t>** out) {
+// empty-subtree roots: empties[k+1] = H(empties[k], empties[k]); 64 sequential hashes on `st` the first
+// time a given empty leaf is seen, then served from the host-side cache (65 felts per leaf value).  The caller
+// holds the library lock (the cache is shared); `s` is the scratch of `st`.
+static int empty_roots(const uint64_t* empty_leaf, const Scratch& s, hipStream_t st, const std::vector<uint64_t>** out) {
   std::vector<uint64_t> key(empty_leaf, empty_leaf + 4);
   auto it = g_empty_cache.find(key);
   if (it == g_empty_cache.end()) {
     uint64_t* d_full = nullptr;
     SP_HIP(hipMalloc(&d_full, 65 * 32));
-    SP_HIP(hipMemcpy(d_full, empty_leaf, 32, hipMemcpyHostToDevice));
+    SP_HIP(hipMemcpyAsync(d_full, key.data(), 32, hipMemcpyHostToDevice, st));
     for (unsigned k2 = 0; k2 < 64; ++k2) {
       const int rc = enqueue_pedersen(d_full + 4 * k2, 1, d_full + 4 * k2, 1, d_full + 4 * (k2 + 1), 1, nullptr,
-                                      s.flag, 1, 0, s, nullptr);
+                                      s.flag, 1, st, s, nullptr);
       if (rc != SP_OK) { (void)hipFree(d_full); return rc; }
     }
     std::vector<uint64_t> all(65 * 4);
-    SP_HIP(hipDeviceSynchronize());
-    SP_HIP(hipMemcpy(all.data(), d_full, 65 * 32, hipMemcpyDeviceToHost));
+    SP_HIP(hipMemcpyAsync(all.data(), d_full, 65 * 32, hipMemcpyDeviceToHost, st));
+    SP_HIP(hipStreamSynchronize(st));
     (void)hipFree(d_full);
     it = g_empty_cache.emplace(key, all).first;
   }
@@ -90,12 +89,14 @@ static int empty_roots(const uint64_t* empty_leaf, const Scratch& s, const std::
 extern "C" int sp_merkle_sparse_root(const uint64_t* keys, const uint64_t* leaves, size_t n,
                                      unsigned height, const uint64_t* empty_leaf, uint64_t* root,
                                      uint8_t* status) {
+  LaneScope ls(ctx_current());
   SP_REQUIRE_READY();
   if (height > 64) { set_error("height must be <= 64"); return SP_ERR_BAD_ARGUMENT; }
   if (!felt_below_p(empty_leaf)) { set_error("empty leaf must be a field element (< p)"); return SP_ERR_BAD_ARGUMENT; }
   if (!keys_ok(height, keys, n, true)) return SP_ERR_BAD_ARGUMENT;
-  Context& c = ctx();
-  ctx_lock lk(c.mu);
+  if (ls.open() != SP_OK) return SP_ERR_HIP;
+  HostLane& L = *ls.lane;
+  hipStream_t st = L.stream;
   // ---- host bookkeeping: induced subtree (merkle_tree.py:18-26) ----
   std::vector<uint64_t> idx(keys, keys + n);
   std::vector<int2> src;                 // all levels, concatenated
@@ -119,59 +120,62 @@ extern "C" int sp_merkle_sparse_root(const uint64_t* keys, const uint64_t* leave
     level_cnt.push_back(nxt.size());
     idx.swap(nxt);
   }
-  // ---- device buffers: empties[height+1], vals ping/pong [n], src ----
-  const size_t nn = n ? n : 1;
-  const size_t fb = nn * 32;
+  // ---- the stream's scratch and the empty-subtree roots (a copy: the cache is the lock's) ----
   const size_t emp_bytes = ((size_t)height + 1) * 32;
-  const size_t src_bytes = ((src.size() + 1) * sizeof(int2) + 63) & ~(size_t)63;
-  const size_t cpt_bytes = 2 * ((size_t)height + 1) * sizeof(aff_packed);
-  SP_HIP(g_sparse_buf.reserve(emp_bytes + 2 * fb + src_bytes + cpt_bytes + 1024));
-  char* b = (char*)g_sparse_buf.ptr;
-  uint64_t* d_emp = (uint64_t*)b;
-  uint64_t* d_a = (uint64_t*)(b + emp_bytes);
-  uint64_t* d_b = (uint64_t*)(b + emp_bytes + fb);
-  int2* d_src = (int2*)(b + emp_bytes + 2 * fb);
-  // the constant points of the levels (SPARSE quad kernel, pedersen.hip), 64-byte aligned behind the child lists
-  aff_packed* d_cpts = (aff_packed*)(((uintptr_t)(b + emp_bytes + 2 * fb + src_bytes) + 63) & ~(uintptr_t)63);
+  std::vector<uint64_t> emp;
   Scratch s;
-  int rc = get_scratch_public(nn, s, 0);
-  if (rc != SP_OK) return rc;
-  SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), 0));
   {
-    const std::vector<uint64_t>* all = nullptr;
-    rc = empty_roots(empty_leaf, s, &all);
+    ctx_lock lk(ctx().mu);
+    int rc = get_scratch_public(n ? n : 1, s, st);
     if (rc != SP_OK) return rc;
-    SP_HIP(hipMemcpy(d_emp, all->data(), emp_bytes, hipMemcpyHostToDevice));
+    SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
+    const std::vector<uint64_t>* all = nullptr;
+    rc = empty_roots(empty_leaf, s, st, &all);
+    if (rc != SP_OK) return rc;
+    emp.assign(all->begin(), all->begin() + emp_bytes / 8);
   }
-  if (n == 0) {
-    SP_HIP(hipDeviceSynchronize());
-    SP_HIP(hipMemcpy(root, d_emp + 4 * height, 32, hipMemcpyDeviceToHost));
+  unsigned f = 0;
+  if (n == 0) {  // nothing to hash: the root of the empty tree
+    std::memcpy(root, &emp[4 * (size_t)height], 32);
   } else {
-    SP_HIP(hipMemcpy(d_a, leaves, n * 32, hipMemcpyHostToDevice));
-    if (!src.empty()) SP_HIP(hipMemcpy(d_src, src.data(), src.size() * sizeof(int2), hipMemcpyHostToDevice));
+    // ---- lane buffer: empties[height + 1] | child lists | leaves (= ping) : what goes up, one piece | pong | points ----
+    const size_t fb = n * 32, src_used = src.size() * sizeof(int2);
+    const size_t src_bytes = (src_used + sizeof(int2) + 63) & ~(size_t)63;
+    const size_t cpt_bytes = 2 * ((size_t)height + 1) * sizeof(aff_packed);
+    const size_t in_bytes = emp_bytes + src_bytes + fb;
+    SP_HIP(L.io.reserve(in_bytes + fb + cpt_bytes + 1024));
+    char* b = (char*)L.io.ptr;
+    uint64_t* d_emp = (uint64_t*)b;
+    int2* d_src = (int2*)(b + emp_bytes);
+    uint64_t* d_a = (uint64_t*)(b + emp_bytes + src_bytes);
+    uint64_t* d_b = (uint64_t*)(b + in_bytes);
+    // the constant points of the levels (SPARSE quad kernel, pedersen.hip), 64-byte aligned behind the values
+    aff_packed* d_cpts = (aff_packed*)(((uintptr_t)(b + in_bytes + fb) + 63) & ~(uintptr_t)63);
+    StagedTrip trip(L.hio, in_bytes, st);
+    SP_HIP(trip.up(d_emp, {{emp.data(), emp_bytes}, {src.data(), src_used}, {nullptr, src_bytes - src_used}, {leaves, fb}}));
     uint64_t *cur = d_a, *nxt = d_b;
-    bool have_cpts = false;
-    if (height > 0) {
-      rc = enqueue_partial_points(d_emp, (int)height, d_cpts, 0, &have_cpts);
-      if (rc != SP_OK) return rc;
+    {
+      ctx_lock lk(ctx().mu);
+      bool have_cpts = false;
+      if (height > 0) {
+        const int rc = enqueue_partial_points(d_emp, (int)height, d_cpts, st, &have_cpts);
+        if (rc != SP_OK) return rc;
+      }
+      for (size_t l = 0; l < level_cnt.size(); ++l) {
+        // gathered mode: operand pointers come from src (children in `cur`, or this level's
+        // empty-subtree root) inside the accumulate kernel - no separate gather pass
+        const int rc = enqueue_pedersen_sparse(cur, d_emp + 4 * l, nxt, s.flag, level_cnt[l], st, s, d_src + level_off[l],
+                                               have_cpts ? d_cpts + 2 * l : nullptr);
+        if (rc != SP_OK) return rc;
+        std::swap(cur, nxt);
+      }
     }
-    for (size_t l = 0; l < level_cnt.size(); ++l) {
-      const size_t m = level_cnt[l];
-      // gathered mode: operand pointers come from src (children in `cur`, or this level's
-      // empty-subtree root) inside the accumulate kernel - no separate gather pass
-      rc = enqueue_pedersen_sparse(cur, d_emp + 4 * l, nxt, s.flag, m, 0, s, d_src + level_off[l],
-                                   have_cpts ? d_cpts + 2 * l : nullptr);
-      if (rc != SP_OK) return rc;
-      std::swap(cur, nxt);
-    }
-    SP_HIP(hipDeviceSynchronize());
-    SP_HIP(hipMemcpy(root, cur, 32, hipMemcpyDeviceToHost));
+    // the root sits in whichever of ping and pong was written last: two small copies, not a staged piece
+    SP_HIP(hipMemcpyAsync(root, cur, 32, hipMemcpyDeviceToHost, st));
+    SP_HIP(hipMemcpyAsync(&f, s.flag, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    SP_HIP(hipStreamSynchronize(st));
   }
-  if (status) {
-    unsigned f = 0;
-    SP_HIP(hipMemcpy(&f, s.flag, sizeof(unsigned), hipMemcpyDeviceToHost));
-    *status = (uint8_t)f;
-  }
+  if (status) *status = (uint8_t)f;
   return SP_OK;
 }
 
@@ -1207,10 +1211,10 @@ static int tree_reserve(SparseTree& t, uint64_t extra) {
 static int tree_empty_roots(const SparseTree& t, std::vector<uint64_t>& out) {
   ctx_lock lk(global_mu());
   Scratch s;
-  int rc = get_scratch_public(1, s, 0);
+  int rc = get_scratch_public(1, s, t.stream);
   if (rc != SP_OK) return rc;
   const std::vector<uint64_t>* emp = nullptr;
-  rc = empty_roots(t.empty_leaf, s, &emp);
+  rc = empty_roots(t.empty_leaf, s, t.stream, &emp);
   if (rc != SP_OK) return rc;
   out.assign(emp->begin(), emp->begin() + 4 * ((size_t)t.height + 1));
   return SP_OK;
@@ -1361,7 +1365,7 @@ static int tree_enqueue(SparseTree& t, const uint64_t* keys, const uint64_t* lea
     SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
     tl_mark("tree: flag cleared");
     const std::vector<uint64_t>* emp = nullptr;
-    rc = empty_roots(t.empty_leaf, s, &emp);
+    rc = empty_roots(t.empty_leaf, s, st, &emp);
     if (rc != SP_OK) return rc;
     tl_mark("tree: empty roots");
     // empty roots + leaves are adjacent in the work buffer (d_emp, then the level-0 values at the start of d_felts):

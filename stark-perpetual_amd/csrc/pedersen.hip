@@ -1682,18 +1682,20 @@ static int merkle_paths_host(const uint64_t* leaves, const uint64_t* siblings, c
   HostLane& L = *ls.lane;
   const size_t total = off[n];
   const size_t n_exp = verify ? n_expected : 0;
-  // device: leaves | siblings | expected | roots | verdict bytes | status bytes
+  // device: leaves | siblings | expected | roots | status bytes | verdict bytes
   const size_t in_bytes = (n + total + n_exp) * 32;
   SP_HIP(L.io.reserve(in_bytes + n * 32 + 2 * n + 64));
   uint64_t* d_leaves = (uint64_t*)L.io.ptr;
   uint64_t* d_sib = d_leaves + 4 * n;
   uint64_t* d_exp = d_sib + 4 * total;
   uint64_t* d_roots = d_exp + 4 * n_exp;
-  uint8_t* d_ver = (uint8_t*)(d_roots + 4 * n);
-  uint8_t* d_st = d_ver + n;
-  SP_HIP(hipMemcpyAsync(d_leaves, leaves, n * 32, hipMemcpyHostToDevice, L.stream));
-  if (total > 0) SP_HIP(hipMemcpyAsync(d_sib, siblings, total * 32, hipMemcpyHostToDevice, L.stream));
-  if (verify) SP_HIP(hipMemcpyAsync(d_exp, expected, n_exp * 32, hipMemcpyHostToDevice, L.stream));
+  uint8_t* d_st = (uint8_t*)(d_roots + 4 * n);
+  uint8_t* d_ver = d_st + n;
+  // what comes back: roots and status bytes (fold), or status and verdict bytes (verify)
+  const std::initializer_list<Piece> folded = {{roots, n * 32}, {status, n}}, checked = {{status, n}, {verdict, n}};
+  const std::initializer_list<Piece>& outs = verify ? checked : folded;
+  StagedTrip trip(L.hio, in_bytes + (verify ? 2 * n : n * 32 + n), L.stream);
+  SP_HIP(trip.up(d_leaves, {{leaves, n * 32}, {siblings, total * 32}, {expected, n_exp * 32}}));
   int rc;
   {
     ctx_lock lk(ctx().mu);
@@ -1701,14 +1703,9 @@ static int merkle_paths_host(const uint64_t* leaves, const uint64_t* siblings, c
                                       n_expected == n ? 1 : 0, verify ? d_ver : nullptr, L.stream);
   }
   if (rc != SP_OK) return rc;
-  if (verify) {
-    SP_HIP(hipMemcpyAsync(verdict, d_ver, n, hipMemcpyDeviceToHost, L.stream));
-    if (status) SP_HIP(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, L.stream));
-  } else {
-    SP_HIP(hipMemcpyAsync(roots, d_roots, n * 32, hipMemcpyDeviceToHost, L.stream));
-    if (status) SP_HIP(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, L.stream));
-  }
+  SP_HIP(trip.down(verify ? (const void*)d_st : d_roots, outs));
   SP_HIP(hipStreamSynchronize(L.stream));
+  trip.finish(outs);
   return SP_OK;
 }
 
@@ -1747,8 +1744,9 @@ int sp_pedersen_batch(const uint64_t* x, const uint64_t* y, uint64_t* out, uint8
   uint64_t* dy = (uint64_t*)((char*)L.io.ptr + fb);
   uint64_t* dout = (uint64_t*)((char*)L.io.ptr + 2 * fb);
   uint8_t* dst = (uint8_t*)L.io.ptr + 3 * fb;
-  SP_HIP(hipMemcpyAsync(dx, x, fb, hipMemcpyHostToDevice, L.stream));
-  SP_HIP(hipMemcpyAsync(dy, y, fb, hipMemcpyHostToDevice, L.stream));
+  const std::initializer_list<Piece> outs = {{out, fb}, {status, n}};
+  StagedTrip trip(L.hio, 3 * fb + n, L.stream);
+  SP_HIP(trip.up(dx, {{x, fb}, {y, fb}}));
   {
     ctx_lock lk(c.mu);  // the per-stream scratch map and the launch bookkeeping
     Scratch s;
@@ -1757,9 +1755,9 @@ int sp_pedersen_batch(const uint64_t* x, const uint64_t* y, uint64_t* out, uint8
     rc = enqueue_pedersen(dx, 1, dy, 1, dout, 1, dst, nullptr, n, L.stream, s, nullptr);
     if (rc != SP_OK) return rc;
   }
-  SP_HIP(hipMemcpyAsync(out, dout, fb, hipMemcpyDeviceToHost, L.stream));
-  if (status) SP_HIP(hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, L.stream));
+  SP_HIP(trip.down(dout, outs));
   SP_HIP(hipStreamSynchronize(L.stream));
+  trip.finish(outs);
   return SP_OK;
 }
 
@@ -1798,26 +1796,28 @@ int sp_profile_end(double* total_ms, uint64_t* launches, uint64_t* units) {
 
 int sp_pedersen_point_batch(const uint64_t* x, const uint64_t* y, uint64_t* ox, uint64_t* oy,
                             uint8_t* status, size_t n) {
+  LaneScope ls(ctx_current());
   SP_REQUIRE_READY();
   if (n == 0) return SP_OK;
+  if (ls.open() != SP_OK) return SP_ERR_HIP;
   Context& c = ctx();
-  ctx_lock lk(c.mu);
+  HostLane& L = *ls.lane;
   const size_t fb = n * 32;
-  SP_HIP(c.io.reserve(4 * fb + n + 64));
-  char* b = (char*)c.io.ptr;
+  SP_HIP(L.io.reserve(4 * fb + n + 64));
+  char* b = (char*)L.io.ptr;
   uint64_t *dx = (uint64_t*)b, *dy = (uint64_t*)(b + fb), *dox = (uint64_t*)(b + 2 * fb),
            *doy = (uint64_t*)(b + 3 * fb);
   uint8_t* dst = (uint8_t*)(b + 4 * fb);
-  SP_HIP(hipMemcpy(dx, x, fb, hipMemcpyHostToDevice));
-  SP_HIP(hipMemcpy(dy, y, fb, hipMemcpyHostToDevice));
-  SP_HIP(hipMemset(dox, 0, 2 * fb));
-  hipLaunchKernelGGL(ped_point_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, 0, dx, dy, n,
+  const std::initializer_list<Piece> outs = {{ox, fb}, {oy, fb}, {status, n}};
+  StagedTrip trip(L.hio, 4 * fb + n, L.stream);
+  SP_HIP(trip.up(dx, {{x, fb}, {y, fb}}));
+  SP_HIP(hipMemsetAsync(dox, 0, 2 * fb, L.stream));  // a rejected item comes back as zeros
+  hipLaunchKernelGGL(ped_point_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, L.stream, dx, dy, n,
                      c.ped, (int)c.plan.bits[0], c.plan.log2e, c.plan.nwin, dox, doy, dst);
   SP_HIP(hipGetLastError());
-  SP_HIP(hipDeviceSynchronize());
-  SP_HIP(hipMemcpy(ox, dox, fb, hipMemcpyDeviceToHost));
-  SP_HIP(hipMemcpy(oy, doy, fb, hipMemcpyDeviceToHost));
-  SP_HIP(hipMemcpy(status, dst, n, hipMemcpyDeviceToHost));
+  SP_HIP(trip.down(dox, outs));
+  SP_HIP(hipStreamSynchronize(L.stream));
+  trip.finish(outs);
   return SP_OK;
 }
 
@@ -1951,62 +1951,61 @@ int sp_merkle_verify_paths(const uint64_t* leaves, const uint64_t* siblings, con
   return merkle_paths_host(leaves, siblings, off, height, keys, n, expected, n_expected, nullptr, verdict, status);
 }
 
+// One chain: sp_pedersen_chains with width 1.
 int sp_pedersen_chain(const uint64_t* elems, size_t n_elems, uint64_t* out, uint8_t* status) {
   SP_REQUIRE_READY();
   if (n_elems < 1) { set_error("chain needs at least one element"); return SP_ERR_BAD_ARGUMENT; }
-  Context& c = ctx();
-  ctx_lock lk(c.mu);
-  SP_HIP(c.io.reserve(n_elems * 32 + 64));
-  uint64_t* d_el = (uint64_t*)c.io.ptr;
-  uint64_t* d_out = (uint64_t*)((char*)c.io.ptr + n_elems * 32);
-  SP_HIP(hipMemcpy(d_el, elems, n_elems * 32, hipMemcpyHostToDevice));
-  uint8_t st8 = 0;
-  int rc = sp_pedersen_chains_dev(d_el, 1, n_elems, d_out, &st8, 0);
-  if (rc != SP_OK) return rc;
-  SP_HIP(hipDeviceSynchronize());
-  SP_HIP(hipMemcpy(out, d_out, 32, hipMemcpyDeviceToHost));
-  if (status) *status = st8;
-  return SP_OK;
+  return sp_pedersen_chains(elems, 1, n_elems, out, status);
 }
 
 // Right fold h = H(e_i, h) from the last element down: the shape of cairo-lang's
 // compute_hash_chain, which the program-hash harness calls
 // (starkware/cairo/bootloaders/program_hash_test_utils.py:9).  Inherently serial: n - 1 launches.
 int sp_pedersen_chain_right(const uint64_t* elems, size_t n_elems, uint64_t* out, uint8_t* status) {
+  LaneScope ls(ctx_current());
   SP_REQUIRE_READY();
   if (n_elems < 1) { set_error("chain needs at least one element"); return SP_ERR_BAD_ARGUMENT; }
-  Context& c = ctx();
-  ctx_lock lk(c.mu);
-  SP_HIP(c.io.reserve((n_elems + 2) * 32 + 64));
-  uint64_t* d_el = (uint64_t*)c.io.ptr;
+  if (ls.open() != SP_OK) return SP_ERR_HIP;
+  HostLane& L = *ls.lane;
+  hipStream_t st = L.stream;
+  // device: elements | ping | pong | the hash that goes back, the status flag behind it
+  const size_t in_bytes = n_elems * 32, out_bytes = 32 + sizeof(unsigned);
+  SP_HIP(L.io.reserve(in_bytes + 64 + out_bytes + 64));
+  uint64_t* d_el = (uint64_t*)L.io.ptr;
   uint64_t* d_a = d_el + 4 * n_elems;
   uint64_t* d_b = d_a + 4;
-  SP_HIP(hipMemcpy(d_el, elems, n_elems * 32, hipMemcpyHostToDevice));
-  Scratch s;
-  int rc = get_scratch(1, s, 0);
-  if (rc != SP_OK) return rc;
-  SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), 0));
-  const uint64_t* h = d_el + 4 * (n_elems - 1);
-  uint64_t* nxt = d_a;
-  bool fused = false;  // the whole fold inside one launch: h = H(e_i, h) for i = n - 2 .. 0 (ped_chain_kernel)
-  if (n_elems >= 3) {
-    rc = enqueue_pedersen_chain(h, d_el + 4 * (n_elems - 2), -1, 1, n_elems - 1, true, d_a, s.flag, 0, &fused);
+  uint64_t* d_out = d_b + 4;
+  StagedTrip trip(L.hio, in_bytes + out_bytes, st);
+  SP_HIP(trip.up(d_el, {{elems, in_bytes}}));
+  {
+    ctx_lock lk(ctx().mu);
+    Scratch s;
+    int rc = get_scratch(1, s, st);
     if (rc != SP_OK) return rc;
-    if (fused) h = d_a;
+    SP_HIP(hipMemsetAsync(s.flag, 0, sizeof(unsigned), st));
+    const uint64_t* h = d_el + 4 * (n_elems - 1);
+    uint64_t* nxt = d_a;
+    bool fused = false;  // the whole fold inside one launch: h = H(e_i, h) for i = n - 2 .. 0 (ped_chain_kernel)
+    if (n_elems >= 3) {
+      rc = enqueue_pedersen_chain(h, d_el + 4 * (n_elems - 2), -1, 1, n_elems - 1, true, d_a, s.flag, st, &fused);
+      if (rc != SP_OK) return rc;
+      if (fused) h = d_a;
+    }
+    for (size_t i = n_elems - 1; !fused && i-- > 0;) {
+      rc = enqueue_pedersen(d_el + 4 * i, 1, h, 1, nxt, 1, nullptr, s.flag, 1, st, s, nullptr);
+      if (rc != SP_OK) return rc;
+      h = nxt;
+      nxt = (nxt == d_a) ? d_b : d_a;
+    }
+    SP_HIP(hipMemcpyAsync(d_out, h, 32, hipMemcpyDeviceToDevice, st));
+    SP_HIP(hipMemcpyAsync(d_out + 4, s.flag, sizeof(unsigned), hipMemcpyDeviceToDevice, st));
   }
-  for (size_t i = n_elems - 1; !fused && i-- > 0;) {
-    rc = enqueue_pedersen(d_el + 4 * i, 1, h, 1, nxt, 1, nullptr, s.flag, 1, 0, s, nullptr);
-    if (rc != SP_OK) return rc;
-    h = nxt;
-    nxt = (nxt == d_a) ? d_b : d_a;
-  }
-  SP_HIP(hipDeviceSynchronize());
-  SP_HIP(hipMemcpy(out, h, 32, hipMemcpyDeviceToHost));
-  if (status) {
-    unsigned f = 0;
-    SP_HIP(hipMemcpy(&f, s.flag, sizeof(unsigned), hipMemcpyDeviceToHost));
-    *status = (uint8_t)f;
-  }
+  unsigned f = 0;
+  const std::initializer_list<Piece> outs = {{out, 32}, {&f, sizeof(unsigned)}};
+  SP_HIP(trip.down(d_out, outs));
+  SP_HIP(hipStreamSynchronize(st));
+  trip.finish(outs);
+  if (status) *status = (uint8_t)f;
   return SP_OK;
 }
 
@@ -2085,21 +2084,27 @@ int sp_commit_rows_dev(const uint64_t* cols, size_t n_rows, size_t n_cols, uint6
 
 int sp_merkle_root(const uint64_t* leaves, unsigned height, uint64_t* root, uint64_t* levels_out,
                    uint8_t* status) {
+  LaneScope ls(ctx_current());
   SP_REQUIRE_READY();
   if (height > 30) { set_error("height too large"); return SP_ERR_BAD_ARGUMENT; }
-  Context& c = ctx();
+  if (ls.open() != SP_OK) return SP_ERR_HIP;
+  HostLane& L = *ls.lane;
   const size_t n0 = (size_t)1 << height;
   const size_t total = 2 * n0 - 1;
-  ctx_lock lk(c.mu);
-  SP_HIP(c.io.reserve(total * 32));
-  uint64_t* d = (uint64_t*)c.io.ptr;
-  SP_HIP(hipMemcpy(d, leaves, n0 * 32, hipMemcpyHostToDevice));
-  uint8_t st8 = 0;
-  int rc = sp_merkle_build_dev(d, height, &st8, 0);
+  SP_HIP(L.io.reserve(total * 32));
+  uint64_t* d = (uint64_t*)L.io.ptr;
+  // what comes back: every level behind the leaves, or the root alone; the caller's leaves are levels_out's start
+  const size_t out_bytes = levels_out ? total * 32 : 32;
+  StagedTrip trip(L.hio, n0 * 32 + out_bytes, L.stream);
+  SP_HIP(trip.up(d, {{leaves, n0 * 32}}));
+  uint8_t st8 = 0;  // written by the stream (the build's status flag), read after the synchronisation below
+  int rc = sp_merkle_build_dev(d, height, &st8, L.stream);
   if (rc != SP_OK) return rc;
-  SP_HIP(hipDeviceSynchronize());
-  SP_HIP(hipMemcpy(root, d + 4 * (total - 1), 32, hipMemcpyDeviceToHost));
-  if (levels_out) SP_HIP(hipMemcpy(levels_out, d, total * 32, hipMemcpyDeviceToHost));
+  const void* d_out = levels_out ? d : d + 4 * (total - 1);
+  SP_HIP(trip.down(d_out, {{levels_out ? levels_out : root, out_bytes}}));
+  SP_HIP(hipStreamSynchronize(L.stream));
+  trip.finish({{levels_out ? levels_out : root, out_bytes}});
+  if (levels_out) std::memcpy(root, levels_out + 4 * (total - 1), 32);
   if (status) *status = st8;
   return SP_OK;
 }

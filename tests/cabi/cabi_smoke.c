@@ -85,6 +85,8 @@ int main(void) {
 
   /* a second life with another window plan: same answers, no state left over */
   if (sp_pedersen_batch(&x[0][0], &y[0][0], &out[0][0], st, 2) != SP_ERR_NOT_INITIALISED) return 28;
+  if (sp_pedersen_chain(&leaves[0][0], 2, chain_out, NULL) != SP_ERR_NOT_INITIALISED) return 28;
+  if (sp_merkle_root(&leaves[0][0], 1, root, NULL, NULL) != SP_ERR_NOT_INITIALISED) return 28;
   if (sp_init(0, 11) != SP_OK || sp_window_bits() != 11) return 29;
   if (sp_pedersen_batch(&x[0][0], &y[0][0], &out[0][0], st, 2) != SP_OK || st[0] || st[1]) return 30;
   if (!felt_eq_hex(out[1], "68cc0b76cddd1dd4ed2301ada9b7c872b23875d5ff837b3a87993e0d9996b87")) return 31;

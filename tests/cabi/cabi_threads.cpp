@@ -74,6 +74,7 @@ struct Data {
 };
 struct Answers {
   Felts hashes, chains, root;
+  Felts scalar;  // the one-item and tree calls of ask_hashing, one behind the other, status bytes included
   std::vector<uint8_t> verdicts, verdicts_point;
   Felts sig_r, sig_s, big_r, big_s;
   Felts tree_roots;  // after each of the three batches
@@ -92,6 +93,23 @@ void ask_hashing(const Data& d, Answers& a) {
   CHECK_RC(sp_pedersen_chains(d.chain_words.data(), 40, 5, a.chains.data(), &cst), "pedersen_chains");
   a.root.assign(4, 0);
   CHECK_RC(sp_merkle_root(d.leaves.data(), 9, a.root.data(), nullptr, &cst), "merkle_root");
+  // chains of 1, 2 and 5 words (5 reaches the fused chain kernel), the right fold, Pedersen points, every level of the
+  // tree, and a height-64 sparse root of 300 keys and of none
+  Felts& o = a.scalar;
+  o.assign(4 * (4 + 2 * 40 + 1023 + 2 + 1) + 40 / 8, 0);
+  uint8_t* sts = (uint8_t*)&o[4 * (4 + 2 * 40 + 1023 + 2)];  // 8 status bytes, then the 40 of the point batch
+  const size_t words[3] = {1, 2, 5};
+  for (int i = 0; i < 3; ++i) CHECK_RC(sp_pedersen_chain(d.chain_words.data(), words[i], &o[4 * i], &sts[i]), "pedersen_chain");
+  CHECK_RC(sp_pedersen_chain_right(d.chain_words.data(), 5, &o[12], &sts[3]), "pedersen_chain_right");
+  CHECK_RC(sp_pedersen_point_batch(d.hx.data(), d.hy.data(), &o[16], &o[16 + 160], &sts[8], 40), "pedersen_point_batch");
+  Felts root(4);
+  CHECK_RC(sp_merkle_root(d.leaves.data(), 9, root.data(), &o[336], &sts[4]), "merkle_root with levels");
+  CHECK_EQ(root, a.root, "merkle_root with and without levels");
+  CHECK_RC(sp_merkle_sparse_root(d.tree_keys[0].data(), d.tree_vals[0].data(), d.n_tree, 64, d.empty_leaf.data(),
+                                 &o[336 + 4 * 1023], &sts[5]), "merkle_sparse_root");
+  CHECK_RC(sp_merkle_sparse_root(nullptr, nullptr, 0, 64, d.empty_leaf.data(), &o[336 + 4 * 1024], &sts[6]),
+           "merkle_sparse_root of no keys");
+  for (int i = 0; i < 48; ++i) CHECK_EQ(sts[i], (uint8_t)0, "scalar status");
 }
 // The signatures whose key index lies in [k0, k1): the two AUTO threads of phase B bring twelve keys each to a
 // 16-slot cache, so each of them finds the cache full of the other's keys again and again (eviction = a new generation).
@@ -297,7 +315,8 @@ int main(int argc, char** argv) {
         case 0:
         case 1:
           ask_hashing(d, a);
-          if (a.hashes != ref.hashes || a.chains != ref.chains || a.root != ref.root) fail("hashing differs", id);
+          if (a.hashes != ref.hashes || a.chains != ref.chains || a.root != ref.root || a.scalar != ref.scalar)
+            fail("hashing differs", id);
           break;
         case 2:
         case 3: {

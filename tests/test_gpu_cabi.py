@@ -42,7 +42,11 @@ def test_host_pointer_entry_points_from_concurrent_threads():
     import random
     import threading
     from oracle import cref
+    from oracle import ref_py as R
     from starkperp import batch
+
+    def hash2(a, b):  # the oracle's tree walk over the C oracle's hash: a Python hash takes milliseconds
+        return cref.pedersen_hash_many([a], [b])[0][0]
 
     def job(seed, out):
         rng = random.Random(seed)
@@ -60,6 +64,12 @@ def test_host_pointer_entry_points_from_concurrent_threads():
                 for w in words[1:]:
                     acc = cref.pedersen_hash_many([acc], [w])[0][0]
                 assert batch.pedersen_chain(words) == acc, (seed, it, "chain")
+                assert batch.pedersen_chain_right(words) == cref.pedersen_chain_right(words), (seed, it, "chain_right")
+                points = batch.pedersen_points_many(xs[:2], ys[:2])
+                assert points == [tuple(R.pedersen_hash_as_point(x, y)) for x, y in zip(xs[:2], ys[:2])], (seed, it, "points")
+                assert batch.merkle_levels(leaves) == cref.merkle_levels(leaves), (seed, it, "levels")
+                mods = {rng.randrange(1 << 16): rng.randrange(P) for _ in range(rng.choice([1, 2, 5]))}
+                assert batch.merkle_sparse_root(16, mods) == R.merkle_multi_update_sparse(16, mods, 0, hash2), (seed, it, "sparse")
             out.append(None)
         except BaseException as e:  # noqa: BLE001 - reported by the main thread
             out.append(e)

@@ -75,6 +75,14 @@ def test_chain(batch):
         for e in el[1:]:
             exp = R.pedersen_hash(exp, e)
         assert batch.pedersen_chain(el) == exp
+    # no element: refused with the call's own text; a caller that does not want the status passes NULL
+    from starkperp import _lib
+    lib, out = _lib.ensure_init(), _lib.new_felts(1)
+    for fn in (lib.sp_pedersen_chain, lib.sp_pedersen_chain_right):
+        assert fn(_lib.pack_felts(el), 0, out, None) == -3 and b"chain needs at least one element" in lib.sp_last_error()
+        assert fn(_lib.pack_felts(el), 5, out, None) == 0
+    assert _lib.unpack_felts(out, 1)[0] == batch.pedersen_chain_right(el)
+    assert lib.sp_pedersen_point_batch(None, None, None, None, None, 0) == 0
 
 
 def test_chains_in_one_launch_vs_c_oracle(batch):
@@ -119,6 +127,11 @@ def test_merkle_small(batch):
         assert batch.merkle_root(lv) == h(g["roots_seed_100_plus_h"][str(hgt)])
     lv = wl.leaves(64, seed=106)
     assert batch.merkle_levels(lv) == R.merkle_levels(lv)
+    from starkperp import _lib
+    lib, root = _lib.ensure_init(), _lib.new_felts(1)
+    assert lib.sp_merkle_root(_lib.pack_felts(lv), 31, root, None, None) == -3 and b"height too large" in lib.sp_last_error()
+    assert lib.sp_merkle_root(_lib.pack_felts(lv), 6, root, None, None) == 0  # no levels, no status asked for
+    assert _lib.unpack_felts(root, 1)[0] == h(g["roots_seed_100_plus_h"]["6"])
 
 
 def test_merkle_c2_full(batch):

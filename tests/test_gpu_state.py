@@ -38,6 +38,7 @@ def test_sparse_roots():
     emp = [h(v) for v in g["empty_roots_leaf0"]]
     for hgt in (0, 1, 5, 64):
         assert batch.merkle_sparse_root(hgt, {}) == emp[hgt]
+    assert batch.merkle_sparse_root(0, {0: 7}) == 7  # a tree of height 0 is its one leaf
     # dense case equals the full rebuild; ragged key patterns vs the oracle
     lv = wl.leaves(32, seed=9)
     assert batch.merkle_sparse_root(5, dict(enumerate(lv))) == R.merkle_root(lv)
