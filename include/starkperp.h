@@ -896,6 +896,44 @@ int sp_builtins_eval_points_dev(unsigned segments, unsigned log_n, const uint64_
                                 const uint64_t* pcur, const uint64_t* pnxt, uint64_t* out, uint8_t* status,
                                 void* stream);
 
+/* Binding a Pedersen proof to its hashes (starkperp.stark.prove_hashes / verify_hashes).  The
+ * Pedersen-step AIR says that SOME hashes were computed.  With n = 2^log_n = 512 k rows, g = w_n and X, Y, H the
+ * polynomials of degree < k that take the public x_i, y_i, h_i at g^(512 i), three boundary quotients say which:
+ *     B(x) = a_0 (s(x) - X(x)) / (x^k - 1) + a_1 (s(x) - Y(x g^-256)) / (x^k + 1) + a_2 (px(x) - H(x g^-511)) / (x^k - g^-k)
+ * (s at row 512 i is x_i, s at row 512 i + 256 is y_i, px at row 512 i + 511 is h_i).  Conventions are those of
+ * sp_air_eval_dev and sp_air_eval_points_dev: DEVICE arrays of packed felts, the three challenges and the shift as
+ * HOST felts, enqueued on `stream`, nothing waited for, the shift neither 0 nor a felt with shift^(4n) = 1 (no
+ * denominator vanishes on such a coset), SP_ERR_BAD_ARGUMENT - sp_last_error() naming the call and the argument -
+ * before anything is launched or written.  The launches of a call are bracketed by sp_profile_begin / sp_profile_end
+ * as one entry (units = points).
+ *
+ * sp_hash_io_boundary_dev: out[j] = (acc ? acc[j] : 0) + B(x_j) mod p for every j < M = 4 n, x_j = shift w_M^j.
+ *     trace_lde    the committed trace LDE, columns col_stride >= M felts apart; only columns 0 (s) and 1 (px) are read
+ *     pub_lde      3 columns of M felts: X, Y, H at x_j, x_j g^-256 and x_j g^-511 - three sp_lde_dev calls of k points
+ *                  at log_blowup 11 with the shifts shift, shift g^-256, shift g^-511
+ *     acc          NULL, or M felts; may be `out`
+ *     log_n        9 .. 24, the range in which sp_lde_dev can produce pub_lde
+ *   x_j^k = shift^k w_2048^j takes 2048 values whatever n is: the call inverts the 3 x 2048 denominators itself, 16
+ *   behind one inversion, into a 192 KiB table per stream - it allocates nothing that grows with M - and then runs
+ *   ONE elementwise launch, seven felts moved and one field reduction per point.
+ * sp_hash_io_boundary_points_dev: B at n_points LDE positions, canonically what the dense call adds at index pos[i].
+ *     coef         3 x k felts: the coefficients of X, Y, H in natural order - sp_ntt_dev(inverse = 1) of the three
+ *                  public columns
+ *     pos[i]       LDE index below M (u64);  cur: n_points x 4 felts, the opened trace row at pos[i]
+ *     out[i]       the value;  status[i] = SP_POINT_OK, or SP_POINT_OUT_OF_RANGE with out[i] = 0 when pos[i] >= M or
+ *                  a felt of the row is not below p (nothing is read out of bounds for any pos[i])
+ *     log_n        9 .. 30;  n_points at most 2^30, 0 is SP_OK without a launch
+ *   One block of 256 lanes per point, the same plan for every k from 1 up: every lane derives x = shift w_M^pos[i] by
+ *   square-and-multiply, takes the coefficients lane, lane + 256, ... of each polynomial by Horner in y^256, scales by
+ *   y^lane; a tree in LDS adds the shares and lane 0 inverts the product of the three denominators once.  About
+ *   3 k / 256 multiplications per lane: nothing proportional to M is built or read. */
+int sp_hash_io_boundary_dev(const uint64_t* trace_lde, size_t col_stride, const uint64_t* pub_lde, unsigned log_n,
+                            const uint64_t* alphas_host, const uint64_t* shift_host, const uint64_t* acc, uint64_t* out,
+                            void* stream);
+int sp_hash_io_boundary_points_dev(unsigned log_n, const uint64_t* coef, const uint64_t* alphas_host,
+                                   const uint64_t* shift_host, size_t n_points, const uint64_t* pos, const uint64_t* cur,
+                                   uint64_t* out, uint8_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ void release_tree_state();      // persistent sparse trees (merkle.hip)
 void release_keys_state();      // square-root tables (keys.hip)
 void release_ec_points_state(); // per-lane ladder tables (ec_points.hip)
 void release_commit_open_state();  // per-stream opening metadata (commit_open.hip)
+void release_hash_io_state();   // per-stream denominator tables (hash_io.hip)
 
 std::recursive_mutex& global_mu() {
   static std::recursive_mutex mu;
@@ -647,6 +648,7 @@ void sp_shutdown(void) {
   sp::release_keys_state();
   sp::release_ec_points_state();
   sp::release_commit_open_state();
+  sp::release_hash_io_state();
   sp::release_tree_state();
   sp::release_host_lanes();
   for (int i = 0; i < SP_MAX_CONTEXTS; ++i) {

@@ -126,6 +126,10 @@ _SIGNATURES = {
                                                 ctypes.c_size_t] + [ctypes.c_void_p] * 5),
     "sp_builtins_eval_points_dev": (ctypes.c_int, [ctypes.c_uint, ctypes.c_uint] + [ctypes.c_void_p] * 6
                                     + [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t] + [ctypes.c_void_p] * 8),
+    "sp_hash_io_boundary_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint]
+                                + [ctypes.c_void_p] * 5),
+    "sp_hash_io_boundary_points_dev": (ctypes.c_int, [ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_size_t] + [ctypes.c_void_p] * 5),
     "sp_tree_create": (ctypes.c_int, [ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
     "sp_tree_create_on": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
     "sp_order_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,

@@ -416,27 +416,32 @@ def prove_trace(trace, air: str, n_queries: int = 8, seed: int = 0, final_log: i
     What this is: the prover-side workload of BASELINE.json configs[3] made checkable end to end.  The
     Fiat-Shamir transcript is chained (statement, then every commitment in order; alpha, every beta and
     the query positions are drawn from it).  What it is not: a sound, complete STARK - no boundary
-    constraint binds the hash inputs / outputs (or `public_inputs`, which are only absorbed), there is
-    no zero knowledge, and the default 8 queries at blowup 4 give about 16 bits.  The reference has no
+    constraint binds the hash inputs / outputs (or `public_inputs`, which are only absorbed; for the
+    Pedersen AIR prove_hashes adds those constraints), there is no zero knowledge, and the default 8 queries at blowup 4 give about 16 bits.  The reference has no
     prover; this path is build-defined and benchmark-grade."""
     return _query_trace(_commit_trace(trace, air, seed, final_log, shift, public_inputs), n_queries)
 
 
-def _commit_trace(trace, air, seed, final_log, shift, public_inputs):
+def _commit_trace(trace, air, seed, final_log, shift, public_inputs, statement=None):
     """The commit phase of prove_trace: every commitment, the transcript up to the final layer.  Returns what the
-    query phase needs."""
+    query phase needs.  `statement` (prove_hashes) = (name, extra, add): the AIR name the transcript and the proof
+    carry instead of `air`, how many challenges are drawn after the AIR's own in the same way, and the function
+    add(trace_lde, comp, extra_alphas) -> comp of what they bring to the composition."""
     P = FIELD_PRIME
     spec = AIRS[air]
+    name, n_extra, add = statement or (air, 0, None)
     n = trace.shape[1]
     M = n << BLOWUP_LOG
-    tr = Transcript(air, n, shift, seed, public_inputs)
+    tr = Transcript(name, n, shift, seed, public_inputs)
     trace_lde = lde(trace)
     lv_trace = commit_rows(trace_lde)
     root_t = root_of(lv_trace)
     tr.absorb("trace_root", root_t)
-    alphas = [tr.challenge("alpha", k) for k in range(spec["n_constraints"])]
+    alphas = [tr.challenge("alpha", k) for k in range(spec["n_constraints"] + n_extra)]
     per = periodic_lde(n, shift, trace.device, air)
-    comp = air_eval(trace_lde, per, n, alphas, shift, air)
+    comp = air_eval(trace_lde, per, n, alphas[:spec["n_constraints"]], shift, air)
+    if add is not None:
+        comp = add(trace_lde, comp, alphas[spec["n_constraints"]:])
     layers, level_bufs, roots = [comp], [], []
     s = shift
     while True:
@@ -454,7 +459,7 @@ def _commit_trace(trace, air, seed, final_log, shift, public_inputs):
     final = tensor_to_felts(layers[-1])
     tr.absorb("final_layer", *final)
     return {"tr": tr, "M": M, "trace_lde": trace_lde, "lv_trace": lv_trace, "layers": layers, "level_bufs": level_bufs,
-            "head": {"n": n, "air": air, "seed": seed, "shift": shift, "public_inputs": list(public_inputs),
+            "head": {"n": n, "air": name, "seed": seed, "shift": shift, "public_inputs": list(public_inputs),
                      "trace_root": root_t, "layer_roots": roots, "final_layer": final}}
 
 
@@ -760,6 +765,202 @@ def verify(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]
     fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
                                 pairs.reshape(len(queries), n_layers, 2, 4), final_t)
     comp, comp_st, fold_st = tensor_to_felts(comp), comp_st.cpu().tolist(), fold_st.cpu().tolist()
+    for qi, (q, j) in enumerate(zip(queries, indices)):
+        trace_ok = [next(openings)[1] for _ in range(4)]
+        layer_ok = [[next(openings)[1] for _ in range(2)] for _ in range(n_layers)]
+        if q["index"] != j:
+            return False, "query index"
+        if [t["row"] for t in q["trace"]] != [j, (j + 4) % m, j + m // 2, (j + m // 2 + 4) % m]:
+            return False, "trace rows"
+        if not all(trace_ok):
+            return False, "trace path"
+        for side in (0, 1):
+            if comp_st[2 * qi + side] != POINT_OK or q["layers"][0][side]["value"] != comp[2 * qi + side]:
+                return False, "composition value"
+        jk, mk = j, m
+        for k in range(n_layers):
+            jk %= mk // 2
+            a, b = q["layers"][k]
+            if (a["pos"], b["pos"]) != (jk, jk + mk // 2):
+                return False, "layer positions"
+            if not all(layer_ok[k]):
+                return False, "layer path"
+            if fold_st[qi][k] != FOLD_OK:
+                return False, "fold consistency at layer %d" % k
+            mk //= 2
+    return True, "ok"
+
+
+# ---- Pedersen proofs that bind their statement: h_i = pedersen_hash(x_i, y_i) for k given triples -----------------
+# DESIGN.md 6.4.  Three boundary quotients join the composition of the Pedersen-step AIR with three more challenges:
+# s at row 512 i is x_i, s at row 512 i + 256 is y_i, px at row 512 i + 511 is h_i.  Definition in integers:
+# tests/hash_io_ref.py (on oracle/stark_ref.py); kernels: csrc/hash_io.hip.
+HASH_IO_AIR = "pedersen_io"
+N_HASH_IO_ALPHAS = 3
+HASH_IO_ROWS = (0, 256, 511)  # the row of a hash's 512 at which x_i, y_i, h_i stand (columns s, s, px)
+
+
+def _root_of_unity(n):
+    return pow(FIELD_GEN, (FIELD_PRIME - 1) // n, FIELD_PRIME)
+
+
+def hash_io_public_lde(public_inputs, n, shift=FIELD_GEN, device="cuda"):
+    """[3, 4n, 4]: the polynomials of degree < k = n / 512 through the x_i, the y_i and the h_i of public_inputs =
+    [x_0, y_0, h_0, x_1, ...] over <g^512>, at the arguments the boundary constraints give them on the LDE coset -
+    x_j, x_j g^-256 and x_j g^-511 for x_j = shift w_4n^j.  Three sp_lde_dev calls of k points at blowup 2048."""
+    torch = _torch()
+    k = n // 512
+    assert len(public_inputs) == 3 * k
+    g = _root_of_unity(n)
+    cols = [lde(felts_to_tensor(public_inputs[c::3], device).unsqueeze(0), 11,
+                shift * pow(g, -r, FIELD_PRIME) % FIELD_PRIME)[0] for c, r in enumerate(HASH_IO_ROWS)]
+    return torch.stack(cols)
+
+
+def hash_io_boundary(trace_lde, pub_lde, n, alphas, shift=FIELD_GEN, acc=None, out=None):
+    """out[j] = (acc[j] if acc is given else 0) + B(x_j) on the whole LDE coset (sp_hash_io_boundary_dev): trace_lde
+    the committed [4, 4n, 4] trace LDE (columns s and px are read), pub_lde from hash_io_public_lde, alphas the three
+    boundary challenges.  `out` may be `acc`."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    M = 4 * n
+    assert len(alphas) == N_HASH_IO_ALPHAS and trace_lde.shape[0] >= 2 and trace_lde.shape[1] == M
+    assert tuple(pub_lde.shape) == (3, M, 4) and pub_lde.is_contiguous()
+    _, _, stride = _table_shape(trace_lde)
+    if out is None:
+        out = torch.empty((M, 4), dtype=torch.int64, device=trace_lde.device)
+    assert tuple(out.shape) == (M, 4) and out.is_contiguous() and (acc is None or (tuple(acc.shape) == (M, 4)
+                                                                                    and acc.is_contiguous()))
+    _lib.check(lib.sp_hash_io_boundary_dev(trace_lde.data_ptr(), stride, pub_lde.data_ptr(), n.bit_length() - 1,
+                                           pack_felts(alphas), pack_felts([shift]),
+                                           None if acc is None else acc.data_ptr(), out.data_ptr(), _stream()),
+               "sp_hash_io_boundary_dev")
+    return out
+
+
+def hash_io_coefficients(public_inputs, n, device="cuda"):
+    """[3, k, 4]: the coefficients, in natural order, of the three public polynomials (three inverse ntt calls; at
+    k = 1 they are the values)."""
+    torch = _torch()
+    cols = [felts_to_tensor(public_inputs[c::3], device) for c in range(3)]
+    return torch.stack([col if n == 512 else ntt(col, inverse=True) for col in cols]).contiguous()
+
+
+def hash_io_boundary_points(n, coef, alphas, shift, pos, cur):
+    """B at arbitrary LDE positions from opened rows (sp_hash_io_boundary_points_dev): coef [3, k, 4] from
+    hash_io_coefficients, pos [q] int64 tensor of LDE indices, cur [q, 4, 4] the trace rows there.  Returns (out
+    [q, 4], status [q] uint8): what hash_io_boundary adds at those indices, and POINT_OK / POINT_OUT_OF_RANGE."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    q = pos.shape[0]
+    assert len(alphas) == N_HASH_IO_ALPHAS and tuple(coef.shape) == (3, n // 512, 4) and coef.is_contiguous()
+    assert pos.dtype == torch.int64 and pos.is_contiguous() and tuple(cur.shape) == (q, 4, 4) and cur.is_contiguous()
+    out = torch.empty((q, 4), dtype=torch.int64, device=cur.device)
+    status = torch.empty((q,), dtype=torch.uint8, device=cur.device)
+    _lib.check(lib.sp_hash_io_boundary_points_dev(n.bit_length() - 1, coef.data_ptr(), pack_felts(alphas),
+                                                  pack_felts([shift]), q, pos.data_ptr(), cur.data_ptr(),
+                                                  out.data_ptr(), status.data_ptr(), _stream()),
+               "sp_hash_io_boundary_points_dev")
+    return out, status
+
+
+def prove_hashes(xs, ys, n_queries: int = 8, seed: int = 0, final_log: int = 6, shift: int = FIELD_GEN, outs=None):
+    """A proof of a statement: h_i = pedersen_hash(x_i, y_i) for the k triples of public_inputs = [x_0, y_0, h_0, x_1,
+    ...].  xs, ys: [k, 4] device tensors as for prove, k a power of two up to 2^15; h_i is read from the trace (px at
+    row 512 i + 511).  `outs`, when given, is the list of CLAIMED outputs, taken instead - it exists so that a test
+    can make the prover lie consistently: such a proof is rejected ("final layer degree").
+
+    What is bound, and was not by prove: both inputs and the output of EVERY hash.  On top of the eleven constraints
+    of the Pedersen-step AIR three boundary quotients with challenges of their own (14 alphas, AIR name
+    "pedersen_io") tie s at rows 512 i and 512 i + 256 and px at row 512 i + 511 to the polynomials through the x_i,
+    y_i and h_i; the composition is sp_air_eval_dev plus sp_hash_io_boundary_dev.  Commitments, FRI and the query
+    phase are prove_trace's and the proof has its shape.  Verifier: verify_hashes (verify answers "malformed").
+
+    What still is not: there is no zero knowledge (the opened rows are trace values), and Q queries at blowup 4 give
+    about 2 Q bits of soundness - the statement is now the right one, the argument is still benchmark-grade."""
+    k = xs.shape[0]
+    assert k >= 1 and k & (k - 1) == 0 and k <= 1 << 15 and tuple(ys.shape) == tuple(xs.shape)
+    n = 512 * k
+    trace = pedersen_trace(xs, ys)
+    hs = tensor_to_felts(trace[1, 511::512]) if outs is None else [int(v) for v in outs]
+    assert len(hs) == k
+    public = [v for triple in zip(tensor_to_felts(xs), tensor_to_felts(ys), hs) for v in triple]
+
+    def add_boundary(trace_lde, comp, alphas):
+        return hash_io_boundary(trace_lde, hash_io_public_lde(public, n, shift, trace_lde.device), n, alphas, shift,
+                                acc=comp, out=comp)
+    c = _commit_trace(trace, "pedersen", seed, final_log, shift, public, (HASH_IO_AIR, N_HASH_IO_ALPHAS, add_boundary))
+    return _query_trace(c, n_queries)
+
+
+def verify_hashes(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]:
+    """Verifier of prove_hashes: (True, "ok") says that h_i = pedersen_hash(x_i, y_i) for every triple of
+    proof["public_inputs"] = [x_0, y_0, h_0, x_1, ...] - inputs and output of every hash are bound by the boundary
+    constraints - up to the soundness of the argument: about 2 Q bits for Q queries at blowup 4, and no zero
+    knowledge.  Reasons, their order and the "malformed" rules are verify's; "public inputs" when the list does not
+    hold 3 n / 512 felts.  A proof of another AIR is "malformed" here, as this AIR is for verify.
+
+    Where it runs: as verify - transcript and comparisons on the host (14 alphas), Merkle openings through
+    check_merkle_openings, folds through sp_fri_check_queries_dev - with the composition value of the 2 Q opened
+    points as the sum (sp_felt_add_dev) of sp_air_eval_points_dev for the eleven AIR constraints and
+    sp_hash_io_boundary_points_dev for the three boundary quotients, which takes the public polynomials'
+    coefficients from three inverse ntt calls made once per proof."""
+    try:
+        if not (isinstance(proof, dict) and proof.get("air") == HASH_IO_AIR):
+            return False, "malformed"
+        view = dict(proof, air="pedersen")  # the shape rules and the Merkle part are the Pedersen AIR's
+        if not (_wellformed(view) and _is_int(final_log) and 0 <= final_log <= 30):
+            return False, "malformed"
+    except Exception:  # an object that misbehaves when inspected is malformed too
+        return False, "malformed"
+    spec = AIRS["pedersen"]
+    n, seed, shift = proof["n"], proof["seed"], proof["shift"]
+    pub = list(proof.get("public_inputs", ()))
+    if len(pub) != 3 * (n // 512) or not all(_is_felt(v) for v in pub):
+        return False, "public inputs"
+    m = n << BLOWUP_LOG
+    log_m = m.bit_length() - 1
+    root_t, roots, final, queries = proof["trace_root"], proof["layer_roots"], proof["final_layer"], proof["queries"]
+    n_layers = log_m - final_log
+    if len(roots) != n_layers or len(final) != 1 << final_log or n_layers < 1:
+        return False, "shape"
+    if n_queries is not None and n_queries != len(queries):
+        return False, "shape"
+    if any(len(q["layers"]) != n_layers for q in queries):
+        return False, "malformed"
+    tr = Transcript(HASH_IO_AIR, n, shift, seed, pub)
+    tr.absorb("trace_root", root_t)
+    alphas = [tr.challenge("alpha", k) for k in range(spec["n_constraints"] + N_HASH_IO_ALPHAS)]
+    betas = []
+    for k in range(n_layers):
+        tr.absorb("layer_root", roots[k])
+        betas.append(tr.challenge("beta", k + 1))
+    tr.absorb("final_layer", *final)
+    indices = [tr.challenge("query", qi, modulus=m // 2) for qi in range(len(queries))]
+    torch = _torch()
+    final_t = felts_to_tensor(final)
+    coeffs = tensor_to_felts(ntt(final_t, inverse=True))
+    if any(c != 0 for c in coeffs[3 * n >> n_layers:]):
+        return False, "final layer degree"
+    if not queries:
+        return True, "ok"
+    openings = iter(check_merkle_openings(view))
+    per = periodic_lde(n, shift, "cuda", "pedersen")
+    dev = per.device
+    positions = torch.tensor([pos for j in indices for pos in (j, j + m // 2)], dtype=torch.int64, device=dev)
+    cur = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side]["values"]], dev)
+    nxt = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side + 1]["values"]], dev)
+    shape = (positions.shape[0], spec["n_cols"], 4)
+    cur, nxt = cur.reshape(shape), nxt.reshape(shape)
+    comp, comp_st = air_eval_points("pedersen", n, per, alphas[:spec["n_constraints"]], shift, positions, cur, nxt)
+    bnd, bnd_st = hash_io_boundary_points(n, hash_io_coefficients(pub, n, dev), alphas[spec["n_constraints"]:], shift,
+                                          positions, cur)
+    comp = felt_add(comp, bnd)
+    pairs = felts_to_tensor([o["value"] for q in queries for pair in q["layers"] for o in pair], dev)
+    fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
+                                pairs.reshape(len(queries), n_layers, 2, 4), final_t)
+    comp, fold_st = tensor_to_felts(comp), fold_st.cpu().tolist()
+    comp_st = [a | b for a, b in zip(comp_st.cpu().tolist(), bnd_st.cpu().tolist())]
     for qi, (q, j) in enumerate(zip(queries, indices)):
         trace_ok = [next(openings)[1] for _ in range(4)]
         layer_ok = [[next(openings)[1] for _ in range(2)] for _ in range(n_layers)]
