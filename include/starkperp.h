@@ -934,6 +934,56 @@ int sp_hash_io_boundary_points_dev(unsigned log_n, const uint64_t* coef, const u
                                    const uint64_t* shift_host, size_t n_points, const uint64_t* pos, const uint64_t* cur,
                                    uint64_t* out, uint8_t* status, void* stream);
 
+/* Boundary constraints from a descriptor (starkperp.stark.prove_signatures / verify_signatures,
+ * prove_ranges / verify_ranges).  The machinery of the hash-io pair above for ANY periodic AIR: period p =
+ * 2^log_period, n = 2^log_n = p k rows, g = w_n, omega = g^p of order k, M = 4 n.  The descriptor, HOST arrays read
+ * before the call returns, names boundary GROUPS - a row o_d below the period each - and TERMS (column c_t, group):
+ * "column c_t at row p i + o_d is v_t[i]" for a public list v_t.  With one challenge a_t per term and C_d the
+ * polynomial of degree < k through sum_{t in d} a_t v_t[i] at omega^i (one public polynomial per GROUP, combined by
+ * the caller before any extension),
+ *     B(x) = sum_d ( sum_{t in d} a_t col_{c_t}(x) - C_d(x g^-o_d) ) / (x^k - w_p^o_d).
+ *     log_period   7 .. 10          n_cols   1 .. 16, the columns of the trace (and of an opened row)
+ *     n_groups     1 .. 4;  group_rows[n_groups] distinct and below p
+ *     n_terms      1 .. 8;  term_cols[t] < n_cols, term_groups[t] < n_groups, every group with at least one term
+ *   The ECDSA AIR is {10, 10, 3, {0, 256, 512}, 5, {0, 0, 3, 4, 0}, {0, 1, 1, 1, 2}}, the range-check AIR
+ *   {7, 1, 1, {0}, 1, {0}, {0}}, and {9, 4, 3, {0, 256, 511}, 3, {0, 0, 1}, {0, 1, 2}} is the hash-io pair: with it
+ *   and pub_lde / coef scaled by the challenges the calls below return what those return, bit for bit.
+ * Conventions are those of the hash-io pair: DEVICE arrays of packed felts, the n_terms challenges (in the
+ * descriptor's term order) and the shift as HOST felts, enqueued on `stream`, nothing waited for, the shift neither 0
+ * nor a felt with shift^(4n) = 1, SP_ERR_BAD_ARGUMENT - sp_last_error() naming the call and the argument - before
+ * anything is launched or written.  The launches of a call are bracketed by sp_profile_begin / sp_profile_end as one
+ * entry (units = points).
+ *
+ * sp_boundary_dev: out[j] = (acc ? acc[j] : 0) + B(x_j) mod p for every j < M, x_j = shift w_M^j.
+ *     trace_lde    the committed trace LDE, columns col_stride >= M felts apart; only the terms' columns are read
+ *     pub_lde      n_groups columns of M felts: C_d at x_j g^-o_d - one sp_lde_dev call per group, k points at
+ *                  log_blowup log_period + 2 with the shift shift g^-o_d
+ *     acc          NULL, or M felts; may be `out`
+ *     log_n        log_period .. 24, the range in which sp_lde_dev can produce pub_lde
+ *   x_j^k = shift^k w_4p^j takes 4 p values whatever n is: the call inverts the n_groups x 4p denominators itself, 16
+ *   behind one inversion, into a table per stream (n_groups * 4p felts: 384 KiB for the ECDSA descriptor) - it
+ *   allocates nothing that grows with M - and then runs ONE elementwise launch: n_terms + 2 n_groups + 1 (+ 1)
+ *   felts moved per point, at most three products behind each field reduction.
+ * sp_boundary_points_dev: B at n_points LDE positions, canonically what the dense call adds at index pos[i].
+ *     coef         n_groups x k felts: the coefficients of the C_d in natural order - sp_ntt_dev(inverse = 1) of the
+ *                  combined public columns
+ *     pos[i]       LDE index below M (u64);  cur: n_points x n_cols felts, the opened trace row at pos[i]
+ *     out[i]       the value;  status[i] = SP_POINT_OK, or SP_POINT_OUT_OF_RANGE with out[i] = 0 when pos[i] >= M or
+ *                  a felt of the row is not below p (nothing is read out of bounds for any pos[i])
+ *     log_n        log_period .. 30;  n_points at most 2^30, 0 is SP_OK without a launch
+ *   One block of 256 lanes per point, the same plan for every k from 1 up: every lane derives x = shift w_M^pos[i] by
+ *   square-and-multiply, takes the coefficients lane, lane + 256, ... of each C_d by Horner in y^256, scales by
+ *   y^lane; a tree in LDS (36 KiB) adds the shares and lane 0 inverts the product of the denominators once. */
+int sp_boundary_dev(unsigned log_period, unsigned n_cols, unsigned n_groups, const unsigned* group_rows,
+                    unsigned n_terms, const unsigned* term_cols, const unsigned* term_groups, const uint64_t* trace_lde,
+                    size_t col_stride, const uint64_t* pub_lde, unsigned log_n, const uint64_t* alphas_host,
+                    const uint64_t* shift_host, const uint64_t* acc, uint64_t* out, void* stream);
+int sp_boundary_points_dev(unsigned log_period, unsigned n_cols, unsigned n_groups, const unsigned* group_rows,
+                           unsigned n_terms, const unsigned* term_cols, const unsigned* term_groups, unsigned log_n,
+                           const uint64_t* coef, const uint64_t* alphas_host, const uint64_t* shift_host,
+                           size_t n_points, const uint64_t* pos, const uint64_t* cur, uint64_t* out, uint8_t* status,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

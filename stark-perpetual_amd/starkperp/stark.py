@@ -417,7 +417,8 @@ def prove_trace(trace, air: str, n_queries: int = 8, seed: int = 0, final_log: i
     Fiat-Shamir transcript is chained (statement, then every commitment in order; alpha, every beta and
     the query positions are drawn from it).  What it is not: a sound, complete STARK - no boundary
     constraint binds the hash inputs / outputs (or `public_inputs`, which are only absorbed; for the
-    Pedersen AIR prove_hashes adds those constraints), there is no zero knowledge, and the default 8 queries at blowup 4 give about 16 bits.  The reference has no
+    Pedersen AIR prove_hashes adds those constraints, for the ECDSA and range-check AIRs prove_signatures and
+    prove_ranges), there is no zero knowledge, and the default 8 queries at blowup 4 give about 16 bits.  The reference has no
     prover; this path is build-defined and benchmark-grade."""
     return _query_trace(_commit_trace(trace, air, seed, final_log, shift, public_inputs), n_queries)
 
@@ -985,6 +986,314 @@ def verify_hashes(proof, final_log: int = 6, n_queries: int = None) -> Tuple[boo
                 return False, "fold consistency at layer %d" % k
             mk //= 2
     return True, "ok"
+
+
+# ---- boundary constraints from a descriptor: ECDSA and range-check proofs that bind their statement --------------
+# DESIGN.md 6.5.  What hash_io does for the Pedersen AIR, general over the AIR: a descriptor names boundary groups (a
+# row below the period each) and terms (column, group); one challenge per term; ONE public polynomial per group.
+# Definition in integers: tests/boundary_ref.py (on oracle/stark_ref.py); kernels: csrc/boundary.hip.
+BOUNDARY_DESCRIPTORS = {
+    # m = z_i at row 0; m = r_i, qx = Qx_i, qy = Qy_i at row 256; m = w_i = s_i^-1 mod N at row 512
+    "ecdsa_io": {"air": "ecdsa", "rows": (0, 256, 512), "terms": ((0, 0), (0, 1), (3, 1), (4, 1), (0, 2))},
+    "range_check_io": {"air": "range_check", "rows": (0,), "terms": ((0, 0),)},  # v = value_i at row 0
+    # the statement of prove_hashes (which keeps its own kernels): the cross-check of the two implementations
+    "pedersen_io": {"air": "pedersen", "rows": HASH_IO_ROWS, "terms": ((0, 0), (0, 1), (1, 2))},
+}
+
+
+def _descriptor(desc):
+    """A descriptor by name, or a dict of one's own: "rows", "terms" as (column, group), and either "air" or
+    "period" and "n_cols" themselves."""
+    return BOUNDARY_DESCRIPTORS[desc] if isinstance(desc, str) else desc
+
+
+def _descriptor_shape(desc):
+    spec = AIRS.get(desc.get("air"), {})
+    return desc.get("period", spec.get("period")), desc.get("n_cols", spec.get("n_cols"))
+
+
+def _descriptor_args(desc):
+    """The seven descriptor arguments of sp_boundary_dev / sp_boundary_points_dev (the arrays must outlive the call:
+    the caller keeps the returned list)."""
+    import ctypes
+    period, n_cols = _descriptor_shape(desc)
+    rows, terms = desc["rows"], desc["terms"]
+    return [period.bit_length() - 1, n_cols, len(rows), (ctypes.c_uint * len(rows))(*rows), len(terms),
+            (ctypes.c_uint * len(terms))(*[c for c, _ in terms]), (ctypes.c_uint * len(terms))(*[d for _, d in terms])]
+
+
+def _inverses_mod(values, modulus):
+    """[v^-1 mod modulus] behind ONE modular inversion (Montgomery's trick): prefix products up, the running inverse
+    down.  Raises ValueError, as pow does, when a value has no inverse."""
+    prefix, run = [], 1
+    for v in values:
+        prefix.append(run)
+        run = run * v % modulus
+    inv, out = pow(run, -1, modulus), [0] * len(prefix)
+    for i in range(len(prefix) - 1, -1, -1):
+        out[i] = inv * prefix[i] % modulus
+        inv = inv * values[i] % modulus
+    return out
+
+
+def boundary_term_values(name, public_inputs):
+    """The public list v_t of every term of a named descriptor from a proof's public inputs."""
+    pub = list(public_inputs)
+    if name == "ecdsa_io":  # [z, r, s, Qx, Qy] per signature; the third ladder's scalar is w = s^-1 mod N
+        return [pub[0::5], pub[1::5], pub[3::5], pub[4::5], _inverses_mod(pub[2::5], EC_ORDER)]
+    if name == "range_check_io":
+        return [pub]
+    if name == "pedersen_io":
+        return [pub[0::3], pub[1::3], pub[2::3]]
+    raise KeyError(name)
+
+
+def _boundary_combined(desc, values, alphas, device):
+    """[n_groups, k, 4]: per group sum_{t in d} a_t v_t[i] - k-sized work in Python integers, before any extension."""
+    torch = _torch()
+    assert len(values) == len(alphas) == len(desc["terms"]) and len({len(v) for v in values}) == 1
+    cols = [[0] * len(values[0]) for _ in desc["rows"]]
+    for (_, d), v, a in zip(desc["terms"], values, alphas):
+        cols[d] = [(acc + a * int(x)) % FIELD_PRIME for acc, x in zip(cols[d], v)]
+    return torch.stack([felts_to_tensor(c, device) for c in cols])
+
+
+def boundary_public_lde(desc, values, n, alphas, shift=FIELD_GEN, device="cuda"):
+    """[n_groups, 4n, 4]: C_d, the polynomial of degree < k = n / period through sum_{t in d} a_t v_t[i] over
+    <g^period>, at x_j g^-o_d for x_j = shift w_4n^j.  `values` = one list of k felts per term, `alphas` the terms'
+    challenges.  One sp_lde_dev call of k points at blowup 4 * period per group."""
+    torch = _torch()
+    desc = _descriptor(desc)
+    period, _ = _descriptor_shape(desc)
+    assert len(values[0]) == n // period
+    g = _root_of_unity(n)
+    comb = _boundary_combined(desc, values, alphas, device)
+    return torch.stack([lde(comb[d].unsqueeze(0), period.bit_length() + 1,
+                            shift * pow(g, -o, FIELD_PRIME) % FIELD_PRIME)[0] for d, o in enumerate(desc["rows"])])
+
+
+def boundary(desc, trace_lde, pub_lde, n, alphas, shift=FIELD_GEN, acc=None, out=None):
+    """out[j] = (acc[j] if acc is given else 0) + B(x_j) on the whole LDE coset (sp_boundary_dev): trace_lde the
+    committed [n_cols, 4n, 4] trace LDE (the terms' columns are read), pub_lde from boundary_public_lde with the same
+    alphas.  `out` may be `acc`."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    desc = _descriptor(desc)
+    M = 4 * n
+    assert len(alphas) == len(desc["terms"]) and trace_lde.shape[0] == _descriptor_shape(desc)[1]
+    assert trace_lde.shape[1] == M and tuple(pub_lde.shape) == (len(desc["rows"]), M, 4) and pub_lde.is_contiguous()
+    _, _, stride = _table_shape(trace_lde)
+    if out is None:
+        out = torch.empty((M, 4), dtype=torch.int64, device=trace_lde.device)
+    assert tuple(out.shape) == (M, 4) and out.is_contiguous() and (acc is None or (tuple(acc.shape) == (M, 4)
+                                                                                    and acc.is_contiguous()))
+    args = _descriptor_args(desc)
+    _lib.check(lib.sp_boundary_dev(*args, trace_lde.data_ptr(), stride, pub_lde.data_ptr(), n.bit_length() - 1,
+                                   pack_felts(alphas), pack_felts([shift]), None if acc is None else acc.data_ptr(),
+                                   out.data_ptr(), _stream()), "sp_boundary_dev")
+    return out
+
+
+def boundary_coefficients(desc, values, n, alphas, device="cuda"):
+    """[n_groups, k, 4]: the coefficients, in natural order, of the C_d (one inverse ntt call per group; at k = 1
+    they are the values)."""
+    torch = _torch()
+    desc = _descriptor(desc)
+    comb = _boundary_combined(desc, values, alphas, device)
+    if comb.shape[1] == 1:
+        return comb.contiguous()
+    return torch.stack([ntt(col, inverse=True) for col in comb]).contiguous()
+
+
+def boundary_points(desc, n, coef, alphas, shift, pos, cur):
+    """B at arbitrary LDE positions from opened rows (sp_boundary_points_dev): coef [n_groups, k, 4] from
+    boundary_coefficients with the same alphas, pos [q] int64 tensor of LDE indices, cur [q, n_cols, 4] the trace rows
+    there.  Returns (out [q, 4], status [q] uint8): what boundary adds at those indices, and POINT_OK /
+    POINT_OUT_OF_RANGE."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    desc = _descriptor(desc)
+    period, n_cols = _descriptor_shape(desc)
+    q = pos.shape[0]
+    assert len(alphas) == len(desc["terms"]) and coef.is_contiguous()
+    assert tuple(coef.shape) == (len(desc["rows"]), n // period, 4)
+    assert pos.dtype == torch.int64 and pos.is_contiguous() and cur.is_contiguous()
+    assert tuple(cur.shape) == (q, n_cols, 4)
+    out = torch.empty((q, 4), dtype=torch.int64, device=cur.device)
+    status = torch.empty((q,), dtype=torch.uint8, device=cur.device)
+    args = _descriptor_args(desc)
+    _lib.check(lib.sp_boundary_points_dev(*args, n.bit_length() - 1, coef.data_ptr(), pack_felts(alphas),
+                                          pack_felts([shift]), q, pos.data_ptr(), cur.data_ptr(), out.data_ptr(),
+                                          status.data_ptr(), _stream()), "sp_boundary_points_dev")
+    return out, status
+
+
+def _prove_bound(name, trace, public, n_queries, seed, final_log, shift):
+    """prove_trace with the boundary quotients of a named descriptor: `public` is absorbed, bound and published."""
+    desc = BOUNDARY_DESCRIPTORS[name]
+    n = trace.shape[1]
+    values = boundary_term_values(name, public)
+
+    def add_boundary(trace_lde, comp, alphas):
+        pub_lde = boundary_public_lde(desc, values, n, alphas, shift, trace_lde.device)
+        return boundary(desc, trace_lde, pub_lde, n, alphas, shift, acc=comp, out=comp)
+    c = _commit_trace(trace, desc["air"], seed, final_log, shift, public, (name, len(desc["terms"]), add_boundary))
+    return _query_trace(c, n_queries)
+
+
+def prove_signatures(msg_hashes, rs, ss, public_keys, n_queries: int = 8, seed: int = 0, final_log: int = 6,
+                     shift: int = FIELD_GEN, claims=None):
+    """A proof of a statement: every (z_i, r_i, s_i, Q_i) of public_inputs = [z_0, r_0, s_0, Qx_0, Qy_0, z_1, ...] is
+    a signature the reference's verify accepts.  Arguments as for prove_ecdsa (Python ints, a power-of-two count up
+    to 2^14).  `claims`, when given, is the public-input list taken INSTEAD of the true one - in the transcript, the
+    composition and FRI alike; it exists so that a test can make the prover lie consistently: such a proof is
+    rejected ("final layer degree").
+
+    What is bound, and was not by prove_ecdsa: on top of the 26 constraints of the ECDSA AIR five boundary terms with
+    challenges of their own (31 alphas, AIR name "ecdsa_io") in three quotients tie the scalar column m at rows
+    1024 i, 1024 i + 256 and 1024 i + 512 to z_i, r_i and w_i = s_i^-1 mod N, and qx, qy at row 1024 i + 256 to Q_i.
+    With the AIR's own gbase, oncurve, addb, rload and fin constraints that is x(w_i (z_i G + r_i Q_i)) = r_i for
+    every i.  The composition is sp_air_eval_ecdsa_dev plus sp_boundary_dev; commitments, FRI and the query phase are
+    prove_trace's and the proof has its shape.  Verifier: verify_signatures (verify answers "malformed").
+
+    What still is not: no zero knowledge, and Q queries at blowup 4 give about 2 Q bits of soundness."""
+    dev = "cuda"
+    k = len(msg_hashes)
+    assert k >= 1 and k & (k - 1) == 0 and k <= 1 << 14 and len(rs) == len(ss) == len(public_keys) == k
+    ws = [pow(s, -1, EC_ORDER) for s in ss]
+    for z, r, w in zip(msg_hashes, rs, ws):
+        assert 0 < z < 2**251 and 1 <= r < 2**251 and 1 <= w < 2**251
+    trace = ecdsa_trace(*(felts_to_tensor(v, dev) for v in (msg_hashes, rs, ws, [q[0] for q in public_keys],
+                                                          [q[1] for q in public_keys])))
+    public = [v for z, r, s, q in zip(msg_hashes, rs, ss, public_keys) for v in (z, r, s, q[0], q[1])]
+    if claims is not None:
+        public = [int(v) for v in claims]
+        assert len(public) == 5 * k
+    return _prove_bound("ecdsa_io", trace, public, n_queries, seed, final_log, shift)
+
+
+def prove_ranges(values, n_queries: int = 8, seed: int = 0, final_log: int = 6, shift: int = FIELD_GEN, claims=None):
+    """A proof of a statement: every value of public_inputs lies in [0, 2^128).  Arguments as for prove_range_checks
+    (a power-of-two count up to 2^17); `claims` as for prove_signatures.  On top of the two constraints of the
+    range-check AIR one boundary quotient with a challenge of its own (3 alphas, AIR name "range_check_io") ties the
+    column at row 128 i to value_i: the decomposed value is the published one.  Verifier: verify_ranges."""
+    values = list(values)
+    k = len(values)
+    assert k >= 1 and k & (k - 1) == 0 and k <= 1 << 17
+    for v in values:
+        assert 0 <= v < FIELD_PRIME
+    trace = range_check_trace(felts_to_tensor(values, "cuda"))
+    public = values if claims is None else [int(v) for v in claims]
+    assert len(public) == k
+    return _prove_bound("range_check_io", trace, public, n_queries, seed, final_log, shift)
+
+
+def _verify_bound(name, proof, final_log, n_queries):
+    """verify_hashes for a named descriptor of BOUNDARY_DESCRIPTORS: the same reasons in the same order."""
+    desc = BOUNDARY_DESCRIPTORS[name]
+    air = desc["air"]
+    try:
+        if not (isinstance(proof, dict) and proof.get("air") == name):
+            return False, "malformed"
+        view = dict(proof, air=air)  # the shape rules, the statement rules and the Merkle part are the base AIR's
+        if not (_wellformed(view) and _is_int(final_log) and 0 <= final_log <= 30):
+            return False, "malformed"
+    except Exception:  # an object that misbehaves when inspected is malformed too
+        return False, "malformed"
+    spec = AIRS[air]
+    n, seed, shift = proof["n"], proof["seed"], proof["shift"]
+    pub = list(proof.get("public_inputs", ()))
+    if not _public_inputs_ok(air, n, pub):
+        return False, "public inputs"
+    m = n << BLOWUP_LOG
+    log_m = m.bit_length() - 1
+    root_t, roots, final, queries = proof["trace_root"], proof["layer_roots"], proof["final_layer"], proof["queries"]
+    n_layers = log_m - final_log
+    if len(roots) != n_layers or len(final) != 1 << final_log or n_layers < 1:
+        return False, "shape"
+    if n_queries is not None and n_queries != len(queries):
+        return False, "shape"
+    if any(len(q["layers"]) != n_layers for q in queries):
+        return False, "malformed"
+    tr = Transcript(name, n, shift, seed, pub)
+    tr.absorb("trace_root", root_t)
+    nc = spec["n_constraints"]
+    alphas = [tr.challenge("alpha", k) for k in range(nc + len(desc["terms"]))]
+    betas = []
+    for k in range(n_layers):
+        tr.absorb("layer_root", roots[k])
+        betas.append(tr.challenge("beta", k + 1))
+    tr.absorb("final_layer", *final)
+    indices = [tr.challenge("query", qi, modulus=m // 2) for qi in range(len(queries))]
+    torch = _torch()
+    final_t = felts_to_tensor(final)
+    coeffs = tensor_to_felts(ntt(final_t, inverse=True))
+    if any(c != 0 for c in coeffs[3 * n >> n_layers:]):
+        return False, "final layer degree"
+    if not queries:
+        return True, "ok"
+    openings = iter(check_merkle_openings(view))
+    per = periodic_lde(n, shift, "cuda", air)
+    dev = per.device
+    positions = torch.tensor([pos for j in indices for pos in (j, j + m // 2)], dtype=torch.int64, device=dev)
+    cur = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side]["values"]], dev)
+    nxt = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side + 1]["values"]], dev)
+    shape = (positions.shape[0], spec["n_cols"], 4)
+    cur, nxt = cur.reshape(shape), nxt.reshape(shape)
+    comp, comp_st = air_eval_points(air, n, per, alphas[:nc], shift, positions, cur, nxt)
+    coef = boundary_coefficients(desc, boundary_term_values(name, pub), n, alphas[nc:], dev)
+    bnd, bnd_st = boundary_points(desc, n, coef, alphas[nc:], shift, positions, cur)
+    comp = felt_add(comp, bnd)
+    pairs = felts_to_tensor([o["value"] for q in queries for pair in q["layers"] for o in pair], dev)
+    fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
+                                pairs.reshape(len(queries), n_layers, 2, 4), final_t)
+    comp, fold_st = tensor_to_felts(comp), fold_st.cpu().tolist()
+    comp_st = [a | b for a, b in zip(comp_st.cpu().tolist(), bnd_st.cpu().tolist())]
+    for qi, (q, j) in enumerate(zip(queries, indices)):
+        trace_ok = [next(openings)[1] for _ in range(4)]
+        layer_ok = [[next(openings)[1] for _ in range(2)] for _ in range(n_layers)]
+        if q["index"] != j:
+            return False, "query index"
+        if [t["row"] for t in q["trace"]] != [j, (j + 4) % m, j + m // 2, (j + m // 2 + 4) % m]:
+            return False, "trace rows"
+        if not all(trace_ok):
+            return False, "trace path"
+        for side in (0, 1):
+            if comp_st[2 * qi + side] != POINT_OK or q["layers"][0][side]["value"] != comp[2 * qi + side]:
+                return False, "composition value"
+        jk, mk = j, m
+        for k in range(n_layers):
+            jk %= mk // 2
+            a, b = q["layers"][k]
+            if (a["pos"], b["pos"]) != (jk, jk + mk // 2):
+                return False, "layer positions"
+            if not all(layer_ok[k]):
+                return False, "layer path"
+            if fold_st[qi][k] != FOLD_OK:
+                return False, "fold consistency at layer %d" % k
+            mk //= 2
+    return True, "ok"
+
+
+def verify_signatures(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]:
+    """Verifier of prove_signatures: (True, "ok") says that x(w_i (z_i G + r_i Q_i)) = r_i with w_i = s_i^-1 mod N for
+    every (z_i, r_i, s_i, Qx_i, Qy_i) of proof["public_inputs"] - up to the soundness of the argument: about 2 Q
+    bits for Q queries at blowup 4, and no zero knowledge.  Reasons, their order and the "malformed" rules are
+    verify's, "public inputs" by the rules of the ECDSA AIR; a proof of another AIR is "malformed" here, as this AIR
+    is for verify.
+
+    Where it runs: as verify_hashes - the composition value of the 2 Q opened points is the sum (sp_felt_add_dev) of
+    sp_air_eval_points_dev for the 26 AIR constraints and sp_boundary_points_dev for the three boundary quotients,
+    which takes the coefficients of the three combined public polynomials from inverse ntt calls made once per proof;
+    w_i is derived from s_i on the host."""
+    return _verify_bound("ecdsa_io", proof, final_log, n_queries)
+
+
+def verify_ranges(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]:
+    """Verifier of prove_ranges: (True, "ok") says that every value of proof["public_inputs"] lies in [0, 2^128) -
+    the decomposed values are the published ones - up to the soundness of the argument.  A sibling of
+    verify_signatures: the same reasons and rules, "public inputs" by the rules of the range-check AIR."""
+    return _verify_bound("range_check_io", proof, final_log, n_queries)
 
 
 # ---- the range-check builtin's encoding and ONE trace for the three builtins (SURVEY 8(f) N4) --------------------
