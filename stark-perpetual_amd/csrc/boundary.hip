@@ -30,8 +30,6 @@
 
 namespace sp {
 
-int air_zinv(const char* who, const uint64_t* shift_host, unsigned log_n, bool times_r2, fe zinv[4]);  // stark.hip
-
 __global__ void __launch_bounds__(BND_TABLE_TPB)
 boundary_table_kernel(BoundaryTableParams prm, uint64_t* __restrict__ table) {
   const unsigned t = blockIdx.x * BND_TABLE_TPB + threadIdx.x;
@@ -61,9 +59,10 @@ boundary_points_kernel(BoundaryTerms tm, BoundaryPointParams prm, const uint64_t
     if (lane == 0) boundary_point_store(false, FE_ZERO, i, out, status);
     return;
   }
-  const fe x = boundary_point_x(prm, pos[i]);
+  const fe x = boundary_point_x(prm.shift, prm.w, prm.log_n, pos[i]);
 #pragma unroll 1
-  for (unsigned d = 0; d < tm.n_groups; ++d) share[d][lane] = boundary_lane_share(prm, tm.log_period, coef, x, d, lane);
+  for (unsigned d = 0; d < tm.n_groups; ++d)
+    share[d][lane] = boundary_lane_share(prm.log_n, tm.log_period, prm.arg[d], coef, x, d, lane);
   __syncthreads();
 #pragma unroll 1
   for (unsigned half = BND_POINT_TPB / 2; half > 0; half >>= 1) {
@@ -83,17 +82,6 @@ static std::map<hipStream_t, DeviceBuffer> g_boundary_table;  // per stream, lik
 void release_boundary_state() {
   for (auto& kv : g_boundary_table) kv.second.release();
   g_boundary_table.clear();
-}
-
-static int refuse(const char* who, const char* bad) {
-  set_error(std::string(who) + ": " + bad);
-  return SP_ERR_BAD_ARGUMENT;
-}
-// the shift rule of the composition calls: below p, not 0, shift^(4n) != 1 (air_zinv names the call and says "shift")
-static int check_shift(const char* who, const uint64_t* shift_host, unsigned log_n) {
-  if (!vf_is_felt(shift_host)) return refuse(who, "bad shift (not below p)");
-  fe unused[4];
-  return air_zinv(who, shift_host, log_n, false, unused);
 }
 
 }  // namespace sp

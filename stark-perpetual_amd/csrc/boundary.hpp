@@ -244,24 +244,27 @@ SP_HD bool boundary_point_ok(unsigned log_n, unsigned n_cols, const uint64_t* po
   for (unsigned c = 0; c < n_cols; ++c) ok = ok & vf_is_felt(cur + 4 * ((size_t)n_cols * i + c));
   return ok;
 }
-// x = shift w_M^pos, most significant bit first (fri_check_item's rule)
-SP_HD fe boundary_point_x(const BoundaryPointParams& prm, uint64_t pos) {
+// The helpers from here to boundary_point_store take plain values, not a parameter struct: hash_io.hip, the
+// three-term instance written out by hand, runs its points kernel on them too (shift, w, arg and log_n are what
+// BoundaryPointParams and HashIoPointParams have in common).
+// x = shift w_M^pos, most significant bit first (fri_check_item's rule); shift and w Montgomery
+SP_HD fe boundary_point_x(const fe& shift, const fe& w, unsigned log_n, uint64_t pos) {
   fe pw = FE_ONE_M;
-  for (int bit = (int)prm.log_n + 1; bit >= 0; --bit) {
+  for (int bit = (int)log_n + 1; bit >= 0; --bit) {
     pw = fe_sqr(pw);
-    if ((pos >> bit) & 1) pw = fe_mul(pw, prm.w);
+    if ((pos >> bit) & 1) pw = fe_mul(pw, w);
   }
-  return fe_mul(prm.shift, pw);
+  return fe_mul(shift, pw);
 }
-// Lane `lane` of a point's block, group d: y^lane * sum_m coef_d[lane + 256 m] (y^256)^m with y = x g^-o_d - the
-// lane's share of C_d(y), Horner in y^256 from its top coefficient down.  Lanes at or above k hold no coefficient and
-// return 0, so one plan serves every k from 1 up.  The running value is plain: a product with the Montgomery power is
-// below p in magnitude, the coefficient adds less than 2^256, the carry pass keeps the limbs below 2^29.  The result
-// is N-form with a value inside (-p, p).
-SP_HD fe boundary_lane_share(const BoundaryPointParams& prm, unsigned log_period, const uint64_t* coef, const fe& x,
+// Lane `lane` of a point's block, group d: y^lane * sum_m coef_d[lane + 256 m] (y^256)^m with y = x * arg, arg =
+// g^-o_d (Montgomery) - the lane's share of C_d(y), Horner in y^256 from its top coefficient down.  Lanes at or above
+// k hold no coefficient and return 0, so one plan serves every k from 1 up.  The running value is plain: a product
+// with the Montgomery power is below p in magnitude, the coefficient adds less than 2^256, the carry pass keeps the
+// limbs below 2^29.  The result is N-form with a value inside (-p, p).
+SP_HD fe boundary_lane_share(unsigned log_n, unsigned log_period, const fe& arg, const uint64_t* coef, const fe& x,
                              unsigned d, unsigned lane) {
-  const size_t k = (size_t)1 << (prm.log_n - log_period);
-  fe pw = fe_mul(x, prm.arg[d]), yl = FE_ONE_M;
+  const size_t k = (size_t)1 << (log_n - log_period);
+  fe pw = fe_mul(x, arg), yl = FE_ONE_M;
   for (unsigned b = 0; b < BND_POINT_TPB_LOG; ++b) {
     if ((lane >> b) & 1) yl = fe_mul(yl, pw);
     pw = fe_sqr(pw);
@@ -272,6 +275,14 @@ SP_HD fe boundary_lane_share(const BoundaryPointParams& prm, unsigned log_period
   fe acc = vf_fe(mine + 4 * BND_POINT_TPB * (count - 1));
   for (size_t m = count - 1; m-- > 0;) acc = fe_carry(fe_add(fe_mul(acc, pw), vf_fe(mine + 4 * BND_POINT_TPB * m)));
   return fe_mul(acc, yl);
+}
+// the two helpers above for a caller that holds the call's own parameter struct
+SP_HD fe boundary_point_x(const BoundaryPointParams& prm, uint64_t pos) {
+  return boundary_point_x(prm.shift, prm.w, prm.log_n, pos);
+}
+SP_HD fe boundary_lane_share(const BoundaryPointParams& prm, unsigned log_period, const uint64_t* coef, const fe& x,
+                             unsigned d, unsigned lane) {
+  return boundary_lane_share(prm.log_n, log_period, prm.arg[d], coef, x, d, lane);
 }
 // one step of the block's tree: both inputs N-form inside (-p, 2p), and so is the sum
 SP_HD fe boundary_share_add(const fe& a, const fe& b) { return fe_weak_reduce(fe_add(a, b)); }

@@ -14,6 +14,7 @@
 #include <map>
 #include <vector>
 
+#include "air_bodies.hpp"
 #include "context.hpp"
 
 namespace sp {
@@ -149,27 +150,12 @@ air_eval_rc16_kernel(const uint64_t* __restrict__ cols, size_t col_stride, const
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M) return;
   const size_t j = (i + 4) & (M - 1);
-  const fe a = ld_plain_m(cols + 4 * i), acc = ld_plain_m(cols + 4 * (col_stride + i)), s = ld_plain_m(cols + 4 * (2 * col_stride + i));
-  const fe an = ld_plain_m(cols + 4 * j), accn = ld_plain_m(cols + 4 * (col_stride + j)), sn = ld_plain_m(cols + 4 * (2 * col_stride + j));
-  const fe pc = ld_plain_m(p + 4 * i), pn = ld_plain_m(p + 4 * j);
-  const fe first8 = ld_plain_m(per + 4 * (i & 31)), step8 = ld_plain_m(per + 4 * (32 + (i & 31)));
+  auto cur = [&](int c) { return ld_plain_m(c < 3 ? cols + 4 * (c * col_stride + i) : p + 4 * i); };
+  auto nxt = [&](int c) { return ld_plain_m(c < 3 ? cols + 4 * (c * col_stride + j) : p + 4 * j); };
+  auto pcol = [&](int c) { return ld_plain_m(per + 4 * (32 * c + (i & 31))); };
   const fe dl = ld_plain_m(d_last + 4 * i), il = ld_plain_m(inv_last + 4 * i), i1 = ld_plain_m(inv_first + 4 * i);
-  // numerators, all Montgomery N-form
-  const fe c0 = fe_mul(first8, fe_sub(acc, a));
-  const fe c1 = fe_mul(step8, fe_carry(fe_sub(fe_sub(accn, fe_mul(acc, prm.two16)), an)));
-  const fe d = fe_carry(fe_sub(sn, s));
-  const fe c2 = fe_mul(d, fe_carry(fe_sub(d, FE_ONE_M)));
-  const fe c3 = fe_mul_sub_mul(pn, fe_carry(fe_sub(prm.z, sn)), pc, fe_carry(fe_sub(prm.z, an)));
-  const fe c4 = fe_carry(fe_sub(fe_mul(pc, fe_carry(fe_sub(prm.z, s))), fe_sub(prm.z, a)));
-  const fe c5 = fe_carry(fe_sub(pc, FE_ONE_M));
-  const fe c6 = fe_carry(fe_sub(s, prm.rc_min));
-  const fe c7 = fe_carry(fe_sub(s, prm.rc_max));
-  const fe t_all = fe_mul_add_mul(prm.alpha[0], c0, prm.alpha[1], c1);
-  const fe t_notlast = fe_mul(fe_mul_add_mul(prm.alpha[2], c2, prm.alpha[3], c3), dl);
-  const fe trans = fe_mul(fe_carry(fe_add(t_all, t_notlast)), prm.zinv[i & 3]);
-  const fe firstp = fe_mul(fe_mul_add_mul(prm.alpha[4], c4, prm.alpha[6], c6), i1);
-  const fe lastp = fe_mul(fe_mul_add_mul(prm.alpha[5], c5, prm.alpha[7], c7), il);
-  st_plain(out + 4 * i, fe_carry(fe_add(fe_add(trans, firstp), lastp)));
+  st_plain(out + 4 * i, air_body_rc16(cur, nxt, pcol, prm.alpha, prm.zinv[i & 3], prm.z, prm.rc_min, prm.rc_max,
+                                      prm.two16, dl, il, i1));
 }
 
 static std::map<hipStream_t, DeviceBuffer> g_builtin_work;
@@ -177,9 +163,6 @@ void release_builtin_state() {
   for (auto& kv : g_builtin_work) kv.second.release();
   g_builtin_work.clear();
 }
-
-// stark.hip: 1 / (x^n - 1) at the four residues i mod 4 of the coset, or SP_ERR_BAD_ARGUMENT for a shift it vanishes on
-int air_zinv(const char* who, const uint64_t* shift_host, unsigned log_n, bool times_r2, fe zinv[4]);
 
 static fe h_pow(fe base_m, uint64_t e) {
   fe r = FE_ONE_M;

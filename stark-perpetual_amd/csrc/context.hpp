@@ -297,6 +297,21 @@ struct LaneScope {
 };
 
 void set_error(const std::string& s);
+// call `who` refuses an argument: "<who>: <bad>" for sp_last_error
+inline int refuse(const char* who, const char* bad) {
+  set_error(std::string(who) + ": " + bad);
+  return SP_ERR_BAD_ARGUMENT;
+}
+// stark.hip: 1 / (x^n - 1) at the four residues i mod 4 of the coset, or SP_ERR_BAD_ARGUMENT for a shift it vanishes on
+int air_zinv(const char* who, const uint64_t* shift_host, unsigned log_n, bool times_r2, fe zinv[4]);
+// the shift rule of the composition calls: below p, not 0, shift^(4n) != 1 (air_zinv names the call and says "shift")
+inline int check_shift(const char* who, const uint64_t* shift_host, unsigned log_n) {
+  u256 sh;
+  std::memcpy(sh.w, shift_host, 32);
+  if (!u256_lt(sh, U256_P)) return refuse(who, "bad shift (not below p)");
+  fe unused[4];
+  return air_zinv(who, shift_host, log_n, false, unused);
+}
 
 // Host-side timeline of ONE traced API call (diagnostics, STARKPERP_TIMELINE=1; tools/c3_probe.py): marks from any
 // thread of the call - the caller's and sp_order_batch's verifier - printed to stderr as one line when the call

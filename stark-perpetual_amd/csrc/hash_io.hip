@@ -25,8 +25,6 @@
 
 namespace sp {
 
-int air_zinv(const char* who, const uint64_t* shift_host, unsigned log_n, bool times_r2, fe zinv[4]);  // stark.hip
-
 __global__ void __launch_bounds__(HIO_TABLE_TPB)
 hash_io_table_kernel(HashIoTableParams prm, uint64_t* __restrict__ table) {
   const unsigned t = blockIdx.x * HIO_TABLE_TPB + threadIdx.x;
@@ -51,23 +49,23 @@ hash_io_points_kernel(HashIoPointParams prm, const uint64_t* __restrict__ coef, 
   const unsigned lane = threadIdx.x;
   // the same for every lane of the block, so the whole block leaves here or none of it does: no barrier is skipped
   if (!hash_io_point_ok(prm.log_n, pos, cur, i)) {
-    if (lane == 0) hash_io_point_store(false, FE_ZERO, i, out, status);
+    if (lane == 0) boundary_point_store(false, FE_ZERO, i, out, status);
     return;
   }
-  const fe x = hash_io_point_x(prm, pos[i]);
+  const fe x = boundary_point_x(prm.shift, prm.w, prm.log_n, pos[i]);
 #pragma unroll 1
-  for (unsigned c = 0; c < 3; ++c) share[c][lane] = hash_io_lane_share(prm, coef, x, c, lane);
+  for (unsigned c = 0; c < 3; ++c) share[c][lane] = boundary_lane_share(prm.log_n, 9, prm.arg[c], coef, x, c, lane);
   __syncthreads();
 #pragma unroll 1
   for (unsigned half = HIO_POINT_TPB / 2; half > 0; half >>= 1) {
     if (lane < half) {
 #pragma unroll 1
-      for (unsigned c = 0; c < 3; ++c) share[c][lane] = hash_io_share_add(share[c][lane], share[c][lane + half]);
+      for (unsigned c = 0; c < 3; ++c) share[c][lane] = boundary_share_add(share[c][lane], share[c][lane + half]);
     }
     __syncthreads();
   }
   if (lane != 0) return;
-  hash_io_point_store(true, hash_io_point_value(prm, x, cur + 16 * i, share[0][0], share[1][0], share[2][0]), i, out,
+  boundary_point_store(true, hash_io_point_value(prm, x, cur + 16 * i, share[0][0], share[1][0], share[2][0]), i, out,
                       status);
 }
 
@@ -75,17 +73,6 @@ static std::map<hipStream_t, DeviceBuffer> g_hash_io_table;  // per stream, like
 void release_hash_io_state() {
   for (auto& kv : g_hash_io_table) kv.second.release();
   g_hash_io_table.clear();
-}
-
-static int refuse(const char* who, const char* bad) {
-  set_error(std::string(who) + ": " + bad);
-  return SP_ERR_BAD_ARGUMENT;
-}
-// the shift rule of the composition calls: below p, not 0, shift^(4n) != 1 (air_zinv names the call and says "shift")
-static int check_shift(const char* who, const uint64_t* shift_host, unsigned log_n) {
-  if (!vf_is_felt(shift_host)) return refuse(who, "bad shift (not below p)");
-  fe unused[4];
-  return air_zinv(who, shift_host, log_n, false, unused);
 }
 
 }  // namespace sp
@@ -126,7 +113,7 @@ int sp_hash_io_boundary_points_dev(unsigned log_n, const uint64_t* coef, const u
   SP_REQUIRE_READY();
   if (const char* bad = hash_io_points_check_args(log_n, n_points)) return refuse(who, bad);
   if (n_points == 0) return SP_OK;
-  if (const char* bad = hash_io_points_check_pointers(coef, alphas_host, shift_host, pos, cur, out, status))
+  if (const char* bad = boundary_points_check_pointers(coef, alphas_host, shift_host, pos, cur, out, status))
     return refuse(who, bad);
   if (const int rc = check_shift(who, shift_host, log_n)) return rc;
   ctx_lock lk(ctx().mu);

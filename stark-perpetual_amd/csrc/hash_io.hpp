@@ -13,7 +13,7 @@
 // inverse denominators, the powers of the evaluation points - are Montgomery; trace values, public columns and
 // coefficients stay plain, so every product (constant) * (value) is the plain product.
 #pragma once
-#include "verify.hpp"
+#include "boundary.hpp"
 
 namespace sp {
 
@@ -41,17 +41,6 @@ SP_HD const char* hash_io_dense_check_args(unsigned log_n, size_t col_stride, co
 SP_HD const char* hash_io_points_check_args(unsigned log_n, size_t n_points) {
   if (log_n < HIO_MIN_LOG_N || log_n > HIO_POINTS_MAX_LOG_N) return "log_n out of range (9 .. 30)";
   if (n_points > VERIFY_MAX_ITEMS) return "n_points above 2^30";
-  return nullptr;
-}
-SP_HD const char* hash_io_points_check_pointers(const void* coef, const void* alphas_host, const void* shift_host,
-                                                const void* pos, const void* cur, const void* out, const void* status) {
-  if (!coef) return "coef is NULL";
-  if (!alphas_host) return "alphas_host is NULL";
-  if (!shift_host) return "shift_host is NULL";
-  if (!pos) return "pos is NULL";
-  if (!cur) return "cur is NULL";
-  if (!out) return "out is NULL";
-  if (!status) return "status is NULL";
   return nullptr;
 }
 
@@ -119,6 +108,9 @@ SP_HD void hash_io_dense_item(const uint64_t* trace, size_t col_stride, const ui
 }
 
 // ---- the points call ----
+// x, a lane's share of X, Y, H (log_period 9, arg[c]), the tree step, the store and the pointer rule are boundary.hpp's
+// boundary_point_x, _lane_share, _share_add, _point_store and _points_check_pointers: one block plan for both calls.
+static_assert(HIO_POINT_TPB == BND_POINT_TPB && HIO_POINT_TPB_LOG == BND_POINT_TPB_LOG, "boundary_lane_share's stride");
 struct HashIoPointParams {
   fe alpha[3];   // Montgomery
   fe shift, w;   // Montgomery: the coset shift, the primitive M-th root of unity
@@ -145,36 +137,21 @@ SP_HD bool hash_io_point_ok(unsigned log_n, const uint64_t* pos, const uint64_t*
   for (unsigned c = 0; c < 4; ++c) ok = ok & vf_is_felt(cur + 4 * (4 * i + c));
   return ok;
 }
-// x = shift w_M^pos, most significant bit first (fri_check_item's rule)
+// The names this call had for the shared helpers, for a caller that holds HashIoPointParams: each is boundary.hpp's.
+inline const char* hash_io_points_check_pointers(const void* coef, const void* alphas_host, const void* shift_host,
+                                                 const void* pos, const void* cur, const void* out, const void* status) {
+  return boundary_points_check_pointers(coef, alphas_host, shift_host, pos, cur, out, status);
+}
 SP_HD fe hash_io_point_x(const HashIoPointParams& prm, uint64_t pos) {
-  fe pw = FE_ONE_M;
-  for (int bit = (int)prm.log_n + 1; bit >= 0; --bit) {
-    pw = fe_sqr(pw);
-    if ((pos >> bit) & 1) pw = fe_mul(pw, prm.w);
-  }
-  return fe_mul(prm.shift, pw);
+  return boundary_point_x(prm.shift, prm.w, prm.log_n, pos);
 }
-// Lane `lane` of a point's block, polynomial c: y^lane * sum_m coef_c[lane + 256 m] (y^256)^m with y = x * arg[c] -
-// the lane's share of sum_i coef_c[i] y^i, Horner in y^256 from its top coefficient down.  Lanes at or above k hold
-// no coefficient and return 0, so one plan serves k = 1 and k = 2^21.  The running value is plain: a product with the
-// Montgomery power is below p in magnitude, the coefficient adds less than 2^256, the carry pass keeps the limbs
-// below 2^29.  The result is N-form with a value inside (-p, p).
 SP_HD fe hash_io_lane_share(const HashIoPointParams& prm, const uint64_t* coef, const fe& x, unsigned c, unsigned lane) {
-  const size_t k = (size_t)1 << (prm.log_n - 9);
-  fe pw = fe_mul(x, prm.arg[c]), yl = FE_ONE_M;
-  for (unsigned b = 0; b < HIO_POINT_TPB_LOG; ++b) {
-    if ((lane >> b) & 1) yl = fe_mul(yl, pw);
-    pw = fe_sqr(pw);
-  }
-  if (lane >= k) return FE_ZERO;
-  const uint64_t* mine = coef + 4 * ((size_t)c * k + lane);
-  const size_t count = (k - lane + HIO_POINT_TPB - 1) / HIO_POINT_TPB;
-  fe acc = vf_fe(mine + 4 * HIO_POINT_TPB * (count - 1));
-  for (size_t m = count - 1; m-- > 0;) acc = fe_carry(fe_add(fe_mul(acc, pw), vf_fe(mine + 4 * HIO_POINT_TPB * m)));
-  return fe_mul(acc, yl);
+  return boundary_lane_share(prm.log_n, 9, prm.arg[c], coef, x, c, lane);
 }
-// one step of the block's tree: both inputs N-form inside (-p, 2p), and so is the sum
-SP_HD fe hash_io_share_add(const fe& a, const fe& b) { return fe_weak_reduce(fe_add(a, b)); }
+SP_HD fe hash_io_share_add(const fe& a, const fe& b) { return boundary_share_add(a, b); }
+SP_HD void hash_io_point_store(bool ok, const fe& value, size_t i, uint64_t* out, uint8_t* status) {
+  boundary_point_store(ok, value, i, out, status);
+}
 // What lane 0 does with the three sums: the three denominators from x^k, ONE inversion for the three of them, the
 // three products behind one reduction as in the dense item.  Canonical.
 SP_HD fe hash_io_point_value(const HashIoPointParams& prm, const fe& x, const uint64_t* cur, const fe& X, const fe& Y,
@@ -189,12 +166,4 @@ SP_HD fe hash_io_point_value(const HashIoPointParams& prm, const fe& x, const ui
   return fe_canon(fe_mul3_add(fe_mul(prm.alpha[0], i0), fe_carry(fe_sub(s, X)), fe_mul(prm.alpha[1], i1),
                               fe_carry(fe_sub(s, Y)), fe_mul(prm.alpha[2], i2), fe_carry(fe_sub(px, H))));
 }
-SP_HD void hash_io_point_store(bool ok, const fe& value, size_t i, uint64_t* out, uint8_t* status) {
-  u256 r;
-  for (int k = 0; k < 8; ++k) r.w[k] = 0;
-  if (ok) r = fe_pack(value);
-  vf_store(out + 4 * i, r);
-  status[i] = ok ? VERIFY_OK : VERIFY_OUT_OF_RANGE;
-}
-
 }  // namespace sp

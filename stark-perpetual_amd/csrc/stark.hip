@@ -19,6 +19,7 @@
 #include <mutex>
 #include <vector>
 
+#include "air_bodies.hpp"
 #include "context.hpp"
 #include "curve_consts.hpp"
 
@@ -807,56 +808,10 @@ air_eval_ecdsa_kernel(const uint64_t* __restrict__ trace /* [10][M] plain */, co
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M) return;
   const size_t in = (i + 4) & (M - 1);
-  auto col = [&](int c, size_t r) { return ld_fe_packed(trace + 4 * ((size_t)c * M + r)); };
+  auto cur = [&](int c) { return ld_fe_packed(trace + 4 * ((size_t)c * M + i)); };
+  auto nxt = [&](int c) { return ld_fe_packed(trace + 4 * ((size_t)c * M + in)); };
   auto pcol = [&](int c) { return ld_fe_packed(per + 4 * ((size_t)c * 4096 + (i & 4095))); };
-  const fe m = col(0, i), px = col(1, i), py = col(2, i), qx = col(3, i), qy = col(4, i), la = col(5, i),
-           ld = col(6, i), cx = col(7, i), cy = col(8, i), cr = col(9, i);
-  const fe m_n = col(0, in), px_n = col(1, in), py_n = col(2, in), qx_n = col(3, in), qy_n = col(4, in),
-           cx_n = col(7, in), cy_n = col(8, in), cr_n = col(9, in);
-  const fe one = {{1, 0, 0, 0, 0, 0, 0, 0, 0}};
-  const fe b = fe_carry(fe_sub(m, fe_dbl(m_n)));
-  const fe bM = fe_to_mont(b), laM = fe_to_mont(la), ldM = fe_to_mont(ld), qxM = fe_to_mont(qx), qyM = fe_to_mont(qy);
-  const fe nbM = fe_carry(fe_sub(FE_ONE_M, bM));
-  const fe qxx = fe_mul(qxM, qx);
-  const fe lala = fe_mul(laM, la);
-  // ladder rows (selector `step`)
-  fe acc = fe_mul(prm.alpha[0], fe_mul(bM, fe_carry(fe_sub(b, one))));
-  auto add = [&](int k, const fe& c) { acc = fe_weak_reduce(fe_add(acc, fe_mul(prm.alpha[k], c))); };
-  add(1, fe_carry(fe_sub(fe_sub(fe_mul(ldM, fe_carry(fe_dbl(qy))), fe_carry(fe_add(fe_dbl(qxx), qxx))), one)));
-  add(2, fe_carry(fe_add(fe_sub(qx_n, fe_mul(ldM, ld)), fe_dbl(qx))));
-  add(3, fe_carry(fe_add(fe_sub(qy_n, fe_mul(ldM, fe_sub(qx, qx_n))), qy)));
-  add(4, fe_mul(bM, fe_carry(fe_sub(fe_mul(laM, fe_sub(px, qx)), fe_sub(py, qy)))));
-  add(5, fe_mul(bM, fe_carry(fe_add(fe_sub(px_n, lala), fe_add(px, qx)))));
-  add(6, fe_mul(bM, fe_carry(fe_add(fe_sub(py_n, fe_mul(laM, fe_sub(px, px_n))), py))));
-  add(7, fe_mul(nbM, fe_carry(fe_sub(px_n, px))));
-  add(8, fe_mul(nbM, fe_carry(fe_sub(py_n, py))));
-  fe total = fe_mul(pcol(0), acc);  // every term below carries the same single 1/R (absorbed by zinv)
-  auto term = [&](const fe& selector, const fe& value) { total = fe_weak_reduce(fe_add(total, fe_mul(selector, value))); };
-  const fe first = pcol(1);
-  term(first, fe_mul(prm.alpha[9], fe_carry(fe_sub(px, prm.sx))));
-  // alpha10 (first * py - start_y): start_y is plain, so alpha10 * start_y is plain and must lose one R like the rest
-  term(first, fe_mul(prm.alpha[10], py));
-  total = fe_weak_reduce(fe_sub(total, fe_mul(one, fe_mul(prm.alpha[10], pcol(2)))));
-  term(pcol(3), fe_mul(prm.alpha[11], m));
-  const fe gbase = pcol(4);
-  term(gbase, fe_mul_add_mul(prm.alpha[12], fe_carry(fe_sub(qx, prm.gx)), prm.alpha[13], fe_carry(fe_sub(qy, prm.gy))));
-  // on-curve: qy^2 - qx^3 - qx - beta
-  term(pcol(5), fe_mul(prm.alpha[14], fe_carry(fe_sub(fe_sub(fe_mul(qyM, qy), fe_mul(qxM, qxx)), fe_add(qx, prm.beta)))));
-  term(pcol(6), fe_mul_add_mul(prm.alpha[15], fe_carry(fe_sub(cx_n, px)), prm.alpha[16], fe_carry(fe_sub(cy_n, py))));
-  term(pcol(7), fe_mul_add_mul(prm.alpha[17], fe_carry(fe_sub(cx_n, cx)), prm.alpha[18], fe_carry(fe_sub(cy_n, cy))));
-  {
-    const fe a0 = fe_carry(fe_sub(fe_mul(laM, fe_sub(px, cx)), fe_sub(py, cy)));
-    const fe a1 = fe_carry(fe_add(fe_sub(qx_n, lala), fe_add(px, cx)));
-    const fe a2 = fe_carry(fe_add(fe_sub(qy_n, fe_mul(laM, fe_sub(px, qx_n))), py));
-    term(pcol(8), fe_mul3_add(prm.alpha[19], a0, prm.alpha[20], a1, prm.alpha[21], a2));
-  }
-  term(pcol(9), fe_mul(prm.alpha[22], fe_carry(fe_sub(cr, m))));
-  term(pcol(10), fe_mul(prm.alpha[23], fe_carry(fe_sub(cr_n, cr))));
-  {
-    const fe f0 = fe_carry(fe_sub(fe_mul(laM, fe_sub(px, prm.sx)), fe_add(py, prm.sy)));
-    const fe f1 = fe_carry(fe_add(fe_sub(cr, lala), fe_add(px, prm.sx)));
-    term(pcol(11), fe_mul_add_mul(prm.alpha[24], f0, prm.alpha[25], f1));
-  }
+  const fe total = air_body_ecdsa(cur, nxt, pcol, prm.alpha, prm.sx, prm.sy, prm.gx, prm.gy, prm.beta);
   st_u256(out + 4 * i, fe_pack(fe_canon(fe_mul(total, prm.zinv[i & 3]))));
 }
 
@@ -876,37 +831,11 @@ air_eval_ec_ladder_kernel(const uint64_t* __restrict__ trace /* [7][M] plain */,
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M) return;
   const size_t in = (i + 4) & (M - 1);
-  auto col = [&](int c, size_t r) { return ld_fe_packed(trace + 4 * ((size_t)c * M + r)); };
+  // the column offset kept apart from the row's: it stays wave-uniform (scalar) arithmetic
+  auto cur = [&](int c) { return ld_fe_packed(trace + 4 * (size_t)c * M + 4 * i); };
+  auto nxt = [&](int c) { return ld_fe_packed(trace + 4 * (size_t)c * M + 4 * in); };
   auto pcol = [&](int c) { return ld_fe_packed(per + 4 * ((size_t)c * 1024 + (i & 1023))); };
-  const fe m = col(0, i), px = col(1, i), py = col(2, i), qx = col(3, i), qy = col(4, i), la = col(5, i),
-           ld = col(6, i);
-  const fe m_n = col(0, in), px_n = col(1, in), py_n = col(2, in), qx_n = col(3, in), qy_n = col(4, in);
-  const fe step = pcol(0), first = pcol(1), z251 = pcol(2);
-  const fe one = {{1, 0, 0, 0, 0, 0, 0, 0, 0}};
-  const fe b = fe_carry(fe_sub(m, fe_dbl(m_n)));
-  const fe bM = fe_to_mont(b), laM = fe_to_mont(la), ldM = fe_to_mont(ld), qxM = fe_to_mont(qx);
-  const fe nbM = fe_carry(fe_sub(FE_ONE_M, bM));
-  fe c[9];
-  c[0] = fe_mul(bM, fe_carry(fe_sub(b, one)));
-  // doubling: ld 2 qy - 3 qx^2 - 1 ; qx' - ld^2 + 2 qx ; qy' - ld (qx - qx') + qy
-  const fe qxx = fe_mul(qxM, qx);
-  c[1] = fe_carry(fe_sub(fe_sub(fe_mul(ldM, fe_carry(fe_dbl(qy))), fe_carry(fe_add(fe_dbl(qxx), qxx))), one));
-  c[2] = fe_carry(fe_add(fe_sub(qx_n, fe_mul(ldM, ld)), fe_dbl(qx)));
-  c[3] = fe_carry(fe_add(fe_sub(qy_n, fe_mul(ldM, fe_sub(qx, qx_n))), qy));
-  // addition (gated by b): la (px - qx) - (py - qy) ; px' - la^2 + px + qx ; py' - la (px - px') + py
-  c[4] = fe_mul(bM, fe_carry(fe_sub(fe_mul(laM, fe_sub(px, qx)), fe_sub(py, qy))));
-  c[5] = fe_mul(bM, fe_carry(fe_add(fe_sub(px_n, fe_mul(laM, la)), fe_add(px, qx))));
-  c[6] = fe_mul(bM, fe_carry(fe_add(fe_sub(py_n, fe_mul(laM, fe_sub(px, px_n))), py)));
-  c[7] = fe_mul(nbM, fe_carry(fe_sub(px_n, px)));
-  c[8] = fe_mul(nbM, fe_carry(fe_sub(py_n, py)));
-  fe acc_step = fe_mul(prm.alpha[0], c[0]);
-#pragma unroll
-  for (int k = 1; k < 9; ++k) acc_step = fe_weak_reduce(fe_add(acc_step, fe_mul(prm.alpha[k], c[k])));
-  fe acc = fe_mul(step, acc_step);
-  const fe firsts = fe_mul_add_mul(prm.alpha[9], fe_carry(fe_sub(px, prm.shift_x)), prm.alpha[10],
-                                   fe_carry(fe_sub(py, prm.shift_y)));
-  acc = fe_weak_reduce(fe_add(acc, fe_mul(first, firsts)));
-  acc = fe_weak_reduce(fe_add(acc, fe_mul(prm.alpha[11], fe_mul(z251, m))));
+  const fe acc = air_body_ec_ladder(cur, nxt, pcol, prm.alpha, prm.shift_x, prm.shift_y);
   st_u256(out + 4 * i, fe_pack(fe_canon(fe_mul(acc, prm.zinv[i & 3]))));
 }
 
@@ -996,32 +925,10 @@ air_eval_kernel(const uint64_t* __restrict__ trace /* [4][col_stride] plain */, 
     in = ii + 4;
     gi = ((t * blk_mul + blk_add) << log_block) + off;
   }
-  auto col = [&](int c, size_t r) { return ld_fe_packed(trace + 4 * ((size_t)c * col_stride + r)); };
+  auto cur = [&](int c) { return ld_fe_packed(trace + 4 * ((size_t)c * col_stride + ii)); };
+  auto nxt = [&](int c) { return ld_fe_packed(trace + 4 * ((size_t)c * col_stride + in)); };
   auto pcol = [&](int c) { return ld_fe_packed(per + 4 * ((size_t)c * 2048 + (gi & 2047))); };
-  const fe s = col(0, ii), px = col(1, ii), py = col(2, ii), lam = col(3, ii);
-  const fe s_n = col(0, in), px_n = col(1, in), py_n = col(2, in);
-  const fe cx = pcol(0), cy = pcol(1), step = pcol(2), mid = pcol(3), end = pcol(4), z252 = pcol(5);
-  const fe one = {{1, 0, 0, 0, 0, 0, 0, 0, 0}};
-  const fe b = fe_carry(fe_sub(s, fe_dbl(s_n)));
-  const fe bM = fe_to_mont(b), lamM = fe_to_mont(lam);
-  const fe nbM = fe_carry(fe_sub(FE_ONE_M, bM));
-  const fe dxn = fe_carry(fe_sub(px_n, px));
-  const fe dyn = fe_carry(fe_sub(py_n, py));
-  // step rows: bM (alpha0 (b - 1) + alpha1 X1 + alpha2 X2 + alpha3 X3) + nbM (alpha4 dx' + alpha5 dy'): sums
-  // of products share one reduction (fe_mul3_add / fe_mul_add_mul), and the common factors bM, nbM
-  // are applied once - about 20 multiplication-equivalents per point instead of 27
-  const fe X1 = fe_carry(fe_sub(fe_mul(lamM, fe_sub(px, cx)), fe_sub(py, cy)));
-  const fe X2 = fe_carry(fe_sub(fe_sub(fe_mul(lamM, lam), px), fe_add(cx, px_n)));
-  const fe X3 = fe_carry(fe_sub(fe_mul(lamM, fe_sub(px, px_n)), fe_add(py, py_n)));
-  const fe in1 = fe_carry(fe_add(fe_mul(prm.alpha[0], fe_carry(fe_sub(b, one))),
-                                 fe_mul3_add(prm.alpha[1], X1, prm.alpha[2], X2, prm.alpha[3], X3)));
-  const fe in2 = fe_mul_add_mul(prm.alpha[4], dxn, prm.alpha[5], dyn);
-  const fe acc_step = fe_mul_add_mul(bM, in1, nbM, in2);
-  const fe mids = fe_mul_add_mul(prm.alpha[6], dxn, prm.alpha[7], dyn);
-  const fe ends = fe_mul_add_mul(prm.alpha[8], fe_carry(fe_sub(px_n, prm.shift_x)), prm.alpha[9],
-                                 fe_carry(fe_sub(py_n, prm.shift_y)));
-  fe acc = fe_mul3_add(step, acc_step, mid, mids, end, ends);
-  acc = fe_weak_reduce(fe_add(acc, fe_mul(prm.alpha[10], fe_mul(z252, s))));
+  const fe acc = air_body_pedersen(cur, nxt, pcol, prm.alpha, prm.shift_x, prm.shift_y);
   st_u256(out + 4 * i, fe_pack(fe_canon(fe_mul(acc, prm.zinv[gi & 3]))));
 }
 

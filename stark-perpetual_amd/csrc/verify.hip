@@ -16,8 +16,6 @@
 
 namespace sp {
 
-int air_zinv(const char* who, const uint64_t* shift_host, unsigned log_n, bool times_r2, fe zinv[4]);  // stark.hip
-
 template <int AIR>
 __global__ void __launch_bounds__(VERIFY_TPB)
 air_points_kernel(unsigned log_n, const uint64_t* __restrict__ per, PointsAirParams prm, size_t n_points,
@@ -36,11 +34,6 @@ fri_check_kernel(unsigned log_m, unsigned n_layers, FriCheckParams prm, size_t n
   const unsigned k = blockIdx.y;
   if (q >= n_queries) return;
   status[q * n_layers + k] = fri_check_item(log_m, n_layers, prm, q, k, index, pairs, final_layer);
-}
-
-static int refuse(const char* who, const char* bad) {
-  set_error(std::string(who) + ": " + bad);
-  return SP_ERR_BAD_ARGUMENT;
 }
 
 }  // namespace sp

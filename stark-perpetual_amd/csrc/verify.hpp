@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "air_bodies.hpp"
 #include "curve_consts.hpp"
 #include "fp29.hpp"
 #include "u256.hpp"
@@ -110,126 +111,42 @@ SP_HD void points_params(int air, const uint64_t* alphas_host, PointsAirParams* 
   prm->beta = fe_unpack(CURVE_BETA);
 }
 
-// The four bodies below are DUPLICATES of the dense composition kernels of stark.hip - the same expressions in the
-// same order on the same lazy-limb bounds, with the row at i read from `cur`, the row at i + 4 from `nxt` and the
-// periodic values from `per` at pos mod (4 * period).  Each names its twin: a change to one is a change to both, and
-// tests/test_gpu_verify.py (dense parity, bit for bit) fails when they part.  The inputs here are felts below p,
-// a subset of the 256-bit values the dense kernels' bounds are stated for.
-//
-// twin: air_eval_kernel (stark.hip), the Pedersen-step AIR
+// The first three bodies below evaluate the constraint functions of air_bodies.hpp - the ones the dense composition
+// kernels of stark.hip evaluate - with the row at i read from `cur`, the row at i + 4 from `nxt` and the periodic
+// values from `per` at pos mod (4 * period).  The inputs here are felts below p, a subset of the 256-bit values the
+// bodies' bounds are stated for.
+struct PointsRow {
+  const uint64_t* row;
+  SP_HD fe operator()(int c) const { return vf_fe(row + 4 * c); }
+};
+struct PointsPeriodic {
+  const uint64_t* per;
+  size_t per_len, at;  // 4 * period, pos mod per_len
+  SP_HD fe operator()(int c) const { return vf_fe(per + 4 * ((size_t)c * per_len + at)); }
+};
 SP_HD fe points_body_pedersen(const uint64_t* cur, const uint64_t* nxt, const uint64_t* per, uint64_t pos,
                               const PointsAirParams& prm) {
-  auto pcol = [&](int c) { return vf_fe(per + 4 * ((size_t)c * 2048 + (pos & 2047))); };
-  const fe s = vf_fe(cur), px = vf_fe(cur + 4), py = vf_fe(cur + 8), lam = vf_fe(cur + 12);
-  const fe s_n = vf_fe(nxt), px_n = vf_fe(nxt + 4), py_n = vf_fe(nxt + 8);
-  const fe cx = pcol(0), cy = pcol(1), step = pcol(2), mid = pcol(3), end = pcol(4), z252 = pcol(5);
-  const fe one = {{1, 0, 0, 0, 0, 0, 0, 0, 0}};
-  const fe b = fe_carry(fe_sub(s, fe_dbl(s_n)));
-  const fe bM = fe_to_mont(b), lamM = fe_to_mont(lam);
-  const fe nbM = fe_carry(fe_sub(FE_ONE_M, bM));
-  const fe dxn = fe_carry(fe_sub(px_n, px));
-  const fe dyn = fe_carry(fe_sub(py_n, py));
-  const fe X1 = fe_carry(fe_sub(fe_mul(lamM, fe_sub(px, cx)), fe_sub(py, cy)));
-  const fe X2 = fe_carry(fe_sub(fe_sub(fe_mul(lamM, lam), px), fe_add(cx, px_n)));
-  const fe X3 = fe_carry(fe_sub(fe_mul(lamM, fe_sub(px, px_n)), fe_add(py, py_n)));
-  const fe in1 = fe_carry(fe_add(fe_mul(prm.alpha[0], fe_carry(fe_sub(b, one))),
-                                 fe_mul3_add(prm.alpha[1], X1, prm.alpha[2], X2, prm.alpha[3], X3)));
-  const fe in2 = fe_mul_add_mul(prm.alpha[4], dxn, prm.alpha[5], dyn);
-  const fe acc_step = fe_mul_add_mul(bM, in1, nbM, in2);
-  const fe mids = fe_mul_add_mul(prm.alpha[6], dxn, prm.alpha[7], dyn);
-  const fe ends = fe_mul_add_mul(prm.alpha[8], fe_carry(fe_sub(px_n, prm.sx)), prm.alpha[9],
-                                 fe_carry(fe_sub(py_n, prm.sy)));
-  fe acc = fe_mul3_add(step, acc_step, mid, mids, end, ends);
-  acc = fe_weak_reduce(fe_add(acc, fe_mul(prm.alpha[10], fe_mul(z252, s))));
+  const fe acc = air_body_pedersen(PointsRow{cur}, PointsRow{nxt}, PointsPeriodic{per, 2048, pos & 2047}, prm.alpha,
+                                   prm.sx, prm.sy);
   return fe_canon(fe_mul(acc, prm.zinv[pos & 3]));
 }
-
-// twin: air_eval_ec_ladder_kernel (stark.hip)
 SP_HD fe points_body_ec_ladder(const uint64_t* cur, const uint64_t* nxt, const uint64_t* per, uint64_t pos,
                                const PointsAirParams& prm) {
-  auto pcol = [&](int c) { return vf_fe(per + 4 * ((size_t)c * 1024 + (pos & 1023))); };
-  const fe m = vf_fe(cur), px = vf_fe(cur + 4), py = vf_fe(cur + 8), qx = vf_fe(cur + 12), qy = vf_fe(cur + 16),
-           la = vf_fe(cur + 20), ld = vf_fe(cur + 24);
-  const fe m_n = vf_fe(nxt), px_n = vf_fe(nxt + 4), py_n = vf_fe(nxt + 8), qx_n = vf_fe(nxt + 12), qy_n = vf_fe(nxt + 16);
-  const fe step = pcol(0), first = pcol(1), z251 = pcol(2);
-  const fe one = {{1, 0, 0, 0, 0, 0, 0, 0, 0}};
-  const fe b = fe_carry(fe_sub(m, fe_dbl(m_n)));
-  const fe bM = fe_to_mont(b), laM = fe_to_mont(la), ldM = fe_to_mont(ld), qxM = fe_to_mont(qx);
-  const fe nbM = fe_carry(fe_sub(FE_ONE_M, bM));
-  fe c[9];
-  c[0] = fe_mul(bM, fe_carry(fe_sub(b, one)));
-  const fe qxx = fe_mul(qxM, qx);
-  c[1] = fe_carry(fe_sub(fe_sub(fe_mul(ldM, fe_carry(fe_dbl(qy))), fe_carry(fe_add(fe_dbl(qxx), qxx))), one));
-  c[2] = fe_carry(fe_add(fe_sub(qx_n, fe_mul(ldM, ld)), fe_dbl(qx)));
-  c[3] = fe_carry(fe_add(fe_sub(qy_n, fe_mul(ldM, fe_sub(qx, qx_n))), qy));
-  c[4] = fe_mul(bM, fe_carry(fe_sub(fe_mul(laM, fe_sub(px, qx)), fe_sub(py, qy))));
-  c[5] = fe_mul(bM, fe_carry(fe_add(fe_sub(px_n, fe_mul(laM, la)), fe_add(px, qx))));
-  c[6] = fe_mul(bM, fe_carry(fe_add(fe_sub(py_n, fe_mul(laM, fe_sub(px, px_n))), py)));
-  c[7] = fe_mul(nbM, fe_carry(fe_sub(px_n, px)));
-  c[8] = fe_mul(nbM, fe_carry(fe_sub(py_n, py)));
-  fe acc_step = fe_mul(prm.alpha[0], c[0]);
-#pragma unroll
-  for (int k = 1; k < 9; ++k) acc_step = fe_weak_reduce(fe_add(acc_step, fe_mul(prm.alpha[k], c[k])));
-  fe acc = fe_mul(step, acc_step);
-  const fe firsts = fe_mul_add_mul(prm.alpha[9], fe_carry(fe_sub(px, prm.sx)), prm.alpha[10],
-                                   fe_carry(fe_sub(py, prm.sy)));
-  acc = fe_weak_reduce(fe_add(acc, fe_mul(first, firsts)));
-  acc = fe_weak_reduce(fe_add(acc, fe_mul(prm.alpha[11], fe_mul(z251, m))));
+  const fe acc = air_body_ec_ladder(PointsRow{cur}, PointsRow{nxt}, PointsPeriodic{per, 1024, pos & 1023}, prm.alpha,
+                                    prm.sx, prm.sy);
   return fe_canon(fe_mul(acc, prm.zinv[pos & 3]));
 }
-
-// twin: air_eval_ecdsa_kernel (stark.hip)
 SP_HD fe points_body_ecdsa(const uint64_t* cur, const uint64_t* nxt, const uint64_t* per, uint64_t pos,
                            const PointsAirParams& prm) {
-  auto pcol = [&](int c) { return vf_fe(per + 4 * ((size_t)c * 4096 + (pos & 4095))); };
-  const fe m = vf_fe(cur), px = vf_fe(cur + 4), py = vf_fe(cur + 8), qx = vf_fe(cur + 12), qy = vf_fe(cur + 16),
-           la = vf_fe(cur + 20), ld = vf_fe(cur + 24), cx = vf_fe(cur + 28), cy = vf_fe(cur + 32), cr = vf_fe(cur + 36);
-  const fe m_n = vf_fe(nxt), px_n = vf_fe(nxt + 4), py_n = vf_fe(nxt + 8), qx_n = vf_fe(nxt + 12), qy_n = vf_fe(nxt + 16),
-           cx_n = vf_fe(nxt + 28), cy_n = vf_fe(nxt + 32), cr_n = vf_fe(nxt + 36);
-  const fe one = {{1, 0, 0, 0, 0, 0, 0, 0, 0}};
-  const fe b = fe_carry(fe_sub(m, fe_dbl(m_n)));
-  const fe bM = fe_to_mont(b), laM = fe_to_mont(la), ldM = fe_to_mont(ld), qxM = fe_to_mont(qx), qyM = fe_to_mont(qy);
-  const fe nbM = fe_carry(fe_sub(FE_ONE_M, bM));
-  const fe qxx = fe_mul(qxM, qx);
-  const fe lala = fe_mul(laM, la);
-  fe acc = fe_mul(prm.alpha[0], fe_mul(bM, fe_carry(fe_sub(b, one))));
-  auto add = [&](int k, const fe& c) { acc = fe_weak_reduce(fe_add(acc, fe_mul(prm.alpha[k], c))); };
-  add(1, fe_carry(fe_sub(fe_sub(fe_mul(ldM, fe_carry(fe_dbl(qy))), fe_carry(fe_add(fe_dbl(qxx), qxx))), one)));
-  add(2, fe_carry(fe_add(fe_sub(qx_n, fe_mul(ldM, ld)), fe_dbl(qx))));
-  add(3, fe_carry(fe_add(fe_sub(qy_n, fe_mul(ldM, fe_sub(qx, qx_n))), qy)));
-  add(4, fe_mul(bM, fe_carry(fe_sub(fe_mul(laM, fe_sub(px, qx)), fe_sub(py, qy)))));
-  add(5, fe_mul(bM, fe_carry(fe_add(fe_sub(px_n, lala), fe_add(px, qx)))));
-  add(6, fe_mul(bM, fe_carry(fe_add(fe_sub(py_n, fe_mul(laM, fe_sub(px, px_n))), py))));
-  add(7, fe_mul(nbM, fe_carry(fe_sub(px_n, px))));
-  add(8, fe_mul(nbM, fe_carry(fe_sub(py_n, py))));
-  fe total = fe_mul(pcol(0), acc);
-  auto term = [&](const fe& selector, const fe& value) { total = fe_weak_reduce(fe_add(total, fe_mul(selector, value))); };
-  const fe first = pcol(1);
-  term(first, fe_mul(prm.alpha[9], fe_carry(fe_sub(px, prm.sx))));
-  term(first, fe_mul(prm.alpha[10], py));
-  total = fe_weak_reduce(fe_sub(total, fe_mul(one, fe_mul(prm.alpha[10], pcol(2)))));
-  term(pcol(3), fe_mul(prm.alpha[11], m));
-  const fe gbase = pcol(4);
-  term(gbase, fe_mul_add_mul(prm.alpha[12], fe_carry(fe_sub(qx, prm.gx)), prm.alpha[13], fe_carry(fe_sub(qy, prm.gy))));
-  term(pcol(5), fe_mul(prm.alpha[14], fe_carry(fe_sub(fe_sub(fe_mul(qyM, qy), fe_mul(qxM, qxx)), fe_add(qx, prm.beta)))));
-  term(pcol(6), fe_mul_add_mul(prm.alpha[15], fe_carry(fe_sub(cx_n, px)), prm.alpha[16], fe_carry(fe_sub(cy_n, py))));
-  term(pcol(7), fe_mul_add_mul(prm.alpha[17], fe_carry(fe_sub(cx_n, cx)), prm.alpha[18], fe_carry(fe_sub(cy_n, cy))));
-  {
-    const fe a0 = fe_carry(fe_sub(fe_mul(laM, fe_sub(px, cx)), fe_sub(py, cy)));
-    const fe a1 = fe_carry(fe_add(fe_sub(qx_n, lala), fe_add(px, cx)));
-    const fe a2 = fe_carry(fe_add(fe_sub(qy_n, fe_mul(laM, fe_sub(px, qx_n))), py));
-    term(pcol(8), fe_mul3_add(prm.alpha[19], a0, prm.alpha[20], a1, prm.alpha[21], a2));
-  }
-  term(pcol(9), fe_mul(prm.alpha[22], fe_carry(fe_sub(cr, m))));
-  term(pcol(10), fe_mul(prm.alpha[23], fe_carry(fe_sub(cr_n, cr))));
-  {
-    const fe f0 = fe_carry(fe_sub(fe_mul(laM, fe_sub(px, prm.sx)), fe_add(py, prm.sy)));
-    const fe f1 = fe_carry(fe_add(fe_sub(cr, lala), fe_add(px, prm.sx)));
-    term(pcol(11), fe_mul_add_mul(prm.alpha[24], f0, prm.alpha[25], f1));
-  }
+  const fe total = air_body_ecdsa(PointsRow{cur}, PointsRow{nxt}, PointsPeriodic{per, 4096, pos & 4095}, prm.alpha,
+                                  prm.sx, prm.sy, prm.gx, prm.gy, prm.beta);
   return fe_canon(fe_mul(total, prm.zinv[pos & 3]));
 }
-
+// The range-check AIR alone is still written twice.  This body is a DUPLICATE of air_eval_range_check_kernel
+// (stark.hip) - the same expressions in the same order on the same lazy-limb bounds; a change to one is a change to
+// both, and tests/test_gpu_verify.py (dense parity, bit for bit) fails when they part.  Sharing it cost that kernel
+// nothing in the code (one shift less) but its launch time missed the A/B margin by a microsecond
+// (profiles/air_bodies_ab.txt), so it stays as it was.
 // twin: air_eval_range_check_kernel (stark.hip)
 SP_HD fe points_body_range_check(const uint64_t* cur, const uint64_t* nxt, const uint64_t* per, uint64_t pos,
                                  const PointsAirParams& prm) {

@@ -17,8 +17,6 @@
 
 namespace sp {
 
-int air_zinv(const char* who, const uint64_t* shift_host, unsigned log_n, bool times_r2, fe zinv[4]);  // stark.hip
-
 __global__ void __launch_bounds__(BSEG_MAX * VERIFY_TPB)
 builtins_points_kernel(BuiltinsPointsArgs g, PointsAirParams ped, PointsAirParams ecd, Rc16PointParams rc) {
   __shared__ fe parts[BSEG_MAX][VERIFY_TPB];
@@ -43,11 +41,6 @@ builtins_points_kernel(BuiltinsPointsArgs g, PointsAirParams ped, PointsAirParam
     ok = ok & (flags[k][lane] != 0);
   }
   builtins_store(sum, ok, i, g.out, g.status);
-}
-
-static int refuse(const char* who, const char* bad) {
-  set_error(std::string(who) + ": " + bad);
-  return SP_ERR_BAD_ARGUMENT;
 }
 
 }  // namespace sp

@@ -98,20 +98,24 @@ SP_HD void rc16_point_params(unsigned log_n, const uint64_t* alphas_host, const 
   prm->g_last = fe_inv(verify_root_of_unity(log_n));
 }
 
-// twin: air_eval_rc16_kernel (builtins.hip) - the same expressions in the same order, C0 .. C7 of
-// oracle/stark_ref.rc16_constraint_values combined as rc16_composition_value.  Like its twin, and unlike the four
-// bodies of verify.hpp, it keeps its Montgomery factors itself: every operand is loaded to Montgomery form (the
-// twin's ld_plain_m), zinv carries no R^2, and the result leaves through fe_from_mont.  Where the twin reads
-// d_last = x - g^(n-1), inv_last = 1 / d_last and inv_first = 1 / (x - 1) from tables over the coset, this derives
-// x = shift w^pos (log_m squarings, most significant bit first) and one inversion of d_last (x - 1).  Neither
+// air_body_rc16 (air_bodies.hpp) at one opened point - the function air_eval_rc16_kernel (builtins.hip) evaluates,
+// C0 .. C7 of oracle/stark_ref.rc16_constraint_values combined as rc16_composition_value.  Like the dense kernel, and
+// unlike the four bodies of verify.hpp, it keeps its Montgomery factors itself: every operand is loaded to Montgomery
+// form (the kernel's ld_plain_m), zinv carries no R^2, and the result leaves through fe_from_mont.  Where the kernel
+// reads d_last = x - g^(n-1), inv_last = 1 / d_last and inv_first = 1 / (x - 1) from tables over the coset, this
+// derives x = shift w^pos (log_m squarings, most significant bit first) and one inversion of d_last (x - 1).  Neither
 // denominator vanishes: 1 and g^(n-1) lie on the trace domain, and a shift with shift^(4n) = 1 is refused.
+struct Rc16PointRow {
+  const uint64_t *row, *p;  // the opened phase-1 row (a, acc, s) and, as column 3, the opened second-phase value
+  SP_HD fe operator()(int c) const { return fe_to_mont(vf_fe(c < 3 ? row + 4 * c : p)); }
+};
+struct Rc16PointPeriodic {
+  const uint64_t* per;
+  uint64_t at;  // pos mod 32
+  SP_HD fe operator()(int c) const { return fe_to_mont(vf_fe(per + 4 * (32 * c + at))); }
+};
 SP_HD fe points_body_rc16(const uint64_t* cur, const uint64_t* nxt, const uint64_t* pcur, const uint64_t* pnxt,
                           const uint64_t* per, uint64_t pos, unsigned log_m, const Rc16PointParams& prm) {
-  auto ld_m = [](const uint64_t* p) { return fe_to_mont(vf_fe(p)); };
-  const fe a = ld_m(cur), acc = ld_m(cur + 4), s = ld_m(cur + 8);
-  const fe an = ld_m(nxt), accn = ld_m(nxt + 4), sn = ld_m(nxt + 8);
-  const fe pc = ld_m(pcur), pn = ld_m(pnxt);
-  const fe first8 = ld_m(per + 4 * (pos & 31)), step8 = ld_m(per + 4 * (32 + (pos & 31)));
   fe pw = FE_ONE_M;  // w^pos
   for (int bit = (int)log_m - 1; bit >= 0; --bit) {
     pw = fe_sqr(pw);
@@ -122,22 +126,8 @@ SP_HD fe points_body_rc16(const uint64_t* cur, const uint64_t* nxt, const uint64
   const fe d1 = fe_carry(fe_sub(x, FE_ONE_M));
   const fe inv = fe_inv(fe_mul(dl, d1));
   const fe il = fe_mul(inv, d1), i1 = fe_mul(inv, dl);
-  // numerators, all Montgomery N-form
-  const fe c0 = fe_mul(first8, fe_sub(acc, a));
-  const fe c1 = fe_mul(step8, fe_carry(fe_sub(fe_sub(accn, fe_mul(acc, prm.two16)), an)));
-  const fe d = fe_carry(fe_sub(sn, s));
-  const fe c2 = fe_mul(d, fe_carry(fe_sub(d, FE_ONE_M)));
-  const fe c3 = fe_mul_sub_mul(pn, fe_carry(fe_sub(prm.z, sn)), pc, fe_carry(fe_sub(prm.z, an)));
-  const fe c4 = fe_carry(fe_sub(fe_mul(pc, fe_carry(fe_sub(prm.z, s))), fe_sub(prm.z, a)));
-  const fe c5 = fe_carry(fe_sub(pc, FE_ONE_M));
-  const fe c6 = fe_carry(fe_sub(s, prm.rc_min));
-  const fe c7 = fe_carry(fe_sub(s, prm.rc_max));
-  const fe t_all = fe_mul_add_mul(prm.alpha[0], c0, prm.alpha[1], c1);
-  const fe t_notlast = fe_mul(fe_mul_add_mul(prm.alpha[2], c2, prm.alpha[3], c3), dl);
-  const fe trans = fe_mul(fe_carry(fe_add(t_all, t_notlast)), prm.zinv[pos & 3]);
-  const fe firstp = fe_mul(fe_mul_add_mul(prm.alpha[4], c4, prm.alpha[6], c6), i1);
-  const fe lastp = fe_mul(fe_mul_add_mul(prm.alpha[5], c5, prm.alpha[7], c7), il);
-  return fe_from_mont(fe_carry(fe_add(fe_add(trans, firstp), lastp)));
+  return fe_from_mont(air_body_rc16(Rc16PointRow{cur, pcur}, Rc16PointRow{nxt, pnxt}, Rc16PointPeriodic{per, pos & 31},
+                                    prm.alpha, prm.zinv[pos & 3], prm.z, prm.rc_min, prm.rc_max, prm.two16, dl, il, i1));
 }
 
 // ---- one point, one segment: what ONE wave of a block does for its lane's point ----

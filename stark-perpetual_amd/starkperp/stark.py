@@ -688,6 +688,141 @@ def _public_inputs_ok(air, n, pub):
     return True
 
 
+# What every verifier here shares, _verify_trace_proof and verify_builtins alike.  Each helper that can fail returns
+# the reason, or None.
+def _fri_shape_reason(proof, n_layers, final_log, n_queries):
+    """The lengths of layer_roots and final_layer, at least one layer, and a given n_queries."""
+    if len(proof["layer_roots"]) != n_layers or len(proof["final_layer"]) != 1 << final_log or n_layers < 1:
+        return "shape"
+    if n_queries is not None and n_queries != len(proof["queries"]):
+        return "shape"
+    if any(len(q["layers"]) != n_layers for q in proof["queries"]):
+        return "malformed"
+    return None
+
+
+def _replay_fri_challenges(tr, proof, m):
+    """The transcript after the alphas: (betas, query indices)."""
+    betas = []
+    for k, root in enumerate(proof["layer_roots"]):
+        tr.absorb("layer_root", root)
+        betas.append(tr.challenge("beta", k + 1))
+    tr.absorb("final_layer", *proof["final_layer"])
+    return betas, [tr.challenge("query", qi, modulus=m // 2) for qi in range(len(proof["queries"]))]
+
+
+def _final_layer_reason(final_t, n, n_layers):
+    """The final layer's interpolant on shift^(2^n_layers) * <w> has the coefficients c_k shift'^k of the inverse
+    transform over <w>, so the zero pattern is the same."""
+    coeffs = tensor_to_felts(ntt(final_t, inverse=True))
+    return "final layer degree" if any(c != 0 for c in coeffs[3 * n >> n_layers:]) else None
+
+
+def _fold_statuses(queries, indices, betas, shift, log_m, final_t, dev):
+    """[q][n_layers] FOLD_* of every fold step of every query, one sp_fri_check_queries_dev launch."""
+    torch = _torch()
+    pairs = felts_to_tensor([o["value"] for q in queries for pair in q["layers"] for o in pair], dev)
+    fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
+                                pairs.reshape(len(queries), len(betas), 2, 4), final_t)
+    return fold_st.cpu().tolist()
+
+
+def _composition_reason(q, qi, comp, comp_st):
+    """Layer 0 of query qi opens the composition column at the two opened points."""
+    for side in (0, 1):
+        if comp_st[2 * qi + side] != POINT_OK or q["layers"][0][side]["value"] != comp[2 * qi + side]:
+            return "composition value"
+    return None
+
+
+def _layers_reason(q, j, m, layer_ok, fold_st):
+    """The layers of one query in the oracle's order: layer_ok[k] the verdicts of layer k's two Merkle openings,
+    fold_st[k] the FOLD_* of the step out of layer k."""
+    jk, mk = j, m
+    for k, (a, b) in enumerate(q["layers"]):
+        jk %= mk // 2
+        if (a["pos"], b["pos"]) != (jk, jk + mk // 2):
+            return "layer positions"
+        if not all(layer_ok[k]):
+            return "layer path"
+        if fold_st[k] != FOLD_OK:
+            return "fold consistency at layer %d" % k
+        mk //= 2
+    return None
+
+
+def _verify_trace_proof(proof, final_log, n_queries, name, air, public_ok, boundary=None):
+    """The one verifier of prove_trace-shaped proofs; verify, verify_hashes, verify_signatures and verify_ranges are
+    its wrappers and document it.  `name` is the AIR name the proof and the transcript carry, `air` the base AIR whose
+    shape rules, constraints and Merkle part apply; public_ok(air, n, pub) is the statement rule.  `boundary`, when
+    given, is (n_extra, f): the transcript yields n_extra more alphas, and f(pub, n, extra_alphas, shift, positions,
+    cur, dev) -> (values, status) at the opened points is added to the composition value (sp_felt_add_dev), its
+    status ORed into the points'."""
+    try:
+        if not (isinstance(proof, dict) and isinstance(air, str) and air in AIR_IDS
+                and proof.get("air", "pedersen") == name):
+            return False, "malformed"
+        view = proof if name == air else dict(proof, air=air)  # shape rules and Merkle part are the base AIR's
+        if not (_wellformed(view) and _is_int(final_log) and 0 <= final_log <= 30):
+            return False, "malformed"
+    except Exception:  # an object that misbehaves when inspected is malformed too
+        return False, "malformed"
+    spec = AIRS[air]
+    n, seed, shift, queries = proof["n"], proof["seed"], proof["shift"], proof["queries"]
+    pub = list(proof.get("public_inputs", ()))
+    if not public_ok(air, n, pub):
+        return False, "public inputs"
+    m = n << BLOWUP_LOG
+    log_m = m.bit_length() - 1
+    n_layers = log_m - final_log
+    reason = _fri_shape_reason(proof, n_layers, final_log, n_queries)
+    if reason:
+        return False, reason
+    nc = spec["n_constraints"]
+    n_extra, boundary_at = boundary or (0, None)
+    tr = Transcript(name, n, shift, seed, pub)
+    tr.absorb("trace_root", proof["trace_root"])
+    alphas = [tr.challenge("alpha", k) for k in range(nc + n_extra)]
+    betas, indices = _replay_fri_challenges(tr, proof, m)
+    torch = _torch()
+    final_t = felts_to_tensor(proof["final_layer"])
+    reason = _final_layer_reason(final_t, n, n_layers)
+    if reason:
+        return False, reason
+    if not queries:
+        return True, "ok"
+    openings = iter(check_merkle_openings(view))
+    per = periodic_lde(n, shift, "cuda", air)
+    dev = per.device
+    positions = torch.tensor([pos for j in indices for pos in (j, j + m // 2)], dtype=torch.int64, device=dev)
+    cur = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side]["values"]], dev)
+    nxt = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side + 1]["values"]], dev)
+    shape = (positions.shape[0], spec["n_cols"], 4)
+    cur, nxt = cur.reshape(shape), nxt.reshape(shape)
+    comp, comp_st = air_eval_points(air, n, per, alphas[:nc], shift, positions, cur, nxt)
+    bnd_st = None
+    if boundary_at:
+        bnd, bnd_st = boundary_at(pub, n, alphas[nc:], shift, positions, cur, dev)
+        comp = felt_add(comp, bnd)
+    fold_st = _fold_statuses(queries, indices, betas, shift, log_m, final_t, dev)
+    comp, comp_st = tensor_to_felts(comp), comp_st.cpu().tolist()
+    if bnd_st is not None:
+        comp_st = [a | b for a, b in zip(comp_st, bnd_st.cpu().tolist())]
+    for qi, (q, j) in enumerate(zip(queries, indices)):
+        trace_ok = [next(openings)[1] for _ in range(4)]
+        layer_ok = [[next(openings)[1] for _ in range(2)] for _ in range(n_layers)]
+        if q["index"] != j:
+            return False, "query index"
+        if [t["row"] for t in q["trace"]] != [j, (j + 4) % m, j + m // 2, (j + m // 2 + 4) % m]:
+            return False, "trace rows"
+        if not all(trace_ok):
+            return False, "trace path"
+        reason = _composition_reason(q, qi, comp, comp_st) or _layers_reason(q, j, m, layer_ok, fold_st[qi])
+        if reason:
+            return False, reason
+    return True, "ok"
+
+
 def verify(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]:
     """Verifier of the proofs of prove_trace and its wrappers (prove, prove_ec_ladders, prove_ecdsa,
     prove_range_checks): returns (ok, reason) with the reasons of oracle/stark_ref.verify_proof, the first failure
@@ -714,82 +849,8 @@ def verify(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]
     if isinstance(proof, dict) and proof.get("air") == "builtins":
         raise ValueError("stark.verify does not take prove_builtins proofs (the builtins verifier is "
                          "stark.verify_builtins)")
-    try:
-        if not (_wellformed(proof) and _is_int(final_log) and 0 <= final_log <= 30):
-            return False, "malformed"
-    except Exception:  # an object that misbehaves when inspected is malformed too
-        return False, "malformed"
-    P = FIELD_PRIME
-    air, n, seed, shift = proof.get("air", "pedersen"), proof["n"], proof["seed"], proof["shift"]
-    spec = AIRS[air]
-    pub = list(proof.get("public_inputs", ()))
-    if not _public_inputs_ok(air, n, pub):
-        return False, "public inputs"
-    m = n << BLOWUP_LOG
-    log_m = m.bit_length() - 1
-    root_t, roots, final, queries = proof["trace_root"], proof["layer_roots"], proof["final_layer"], proof["queries"]
-    n_layers = log_m - final_log
-    if len(roots) != n_layers or len(final) != 1 << final_log or n_layers < 1:
-        return False, "shape"
-    if n_queries is not None and n_queries != len(queries):
-        return False, "shape"
-    if any(len(q["layers"]) != n_layers for q in queries):
-        return False, "malformed"
-    tr = Transcript(air, n, shift, seed, pub)
-    tr.absorb("trace_root", root_t)
-    alphas = [tr.challenge("alpha", k) for k in range(spec["n_constraints"])]
-    betas = []
-    for k in range(n_layers):
-        tr.absorb("layer_root", roots[k])
-        betas.append(tr.challenge("beta", k + 1))
-    tr.absorb("final_layer", *final)
-    indices = [tr.challenge("query", qi, modulus=m // 2) for qi in range(len(queries))]
-    # the final layer: its interpolant on shift^(2^n_layers) * <w> has the coefficients c_k shift'^k of the inverse
-    # transform over <w>, so the zero pattern is the same
-    torch = _torch()
-    final_t = felts_to_tensor(final)
-    coeffs = tensor_to_felts(ntt(final_t, inverse=True))
-    if any(c != 0 for c in coeffs[3 * n >> n_layers:]):
-        return False, "final layer degree"
-    if not queries:
-        return True, "ok"
-    openings = iter(check_merkle_openings(proof))
-    per = periodic_lde(n, shift, "cuda", air)
-    dev = per.device
-    positions = [pos for j in indices for pos in (j, j + m // 2)]
-    cur = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side]["values"]], dev)
-    nxt = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side + 1]["values"]], dev)
-    shape = (len(positions), spec["n_cols"], 4)
-    comp, comp_st = air_eval_points(air, n, per, alphas, shift, torch.tensor(positions, dtype=torch.int64, device=dev),
-                                    cur.reshape(shape), nxt.reshape(shape))
-    pairs = felts_to_tensor([o["value"] for q in queries for pair in q["layers"] for o in pair], dev)
-    fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
-                                pairs.reshape(len(queries), n_layers, 2, 4), final_t)
-    comp, comp_st, fold_st = tensor_to_felts(comp), comp_st.cpu().tolist(), fold_st.cpu().tolist()
-    for qi, (q, j) in enumerate(zip(queries, indices)):
-        trace_ok = [next(openings)[1] for _ in range(4)]
-        layer_ok = [[next(openings)[1] for _ in range(2)] for _ in range(n_layers)]
-        if q["index"] != j:
-            return False, "query index"
-        if [t["row"] for t in q["trace"]] != [j, (j + 4) % m, j + m // 2, (j + m // 2 + 4) % m]:
-            return False, "trace rows"
-        if not all(trace_ok):
-            return False, "trace path"
-        for side in (0, 1):
-            if comp_st[2 * qi + side] != POINT_OK or q["layers"][0][side]["value"] != comp[2 * qi + side]:
-                return False, "composition value"
-        jk, mk = j, m
-        for k in range(n_layers):
-            jk %= mk // 2
-            a, b = q["layers"][k]
-            if (a["pos"], b["pos"]) != (jk, jk + mk // 2):
-                return False, "layer positions"
-            if not all(layer_ok[k]):
-                return False, "layer path"
-            if fold_st[qi][k] != FOLD_OK:
-                return False, "fold consistency at layer %d" % k
-            mk //= 2
-    return True, "ok"
+    air = proof.get("air", "pedersen") if isinstance(proof, dict) else None
+    return _verify_trace_proof(proof, final_log, n_queries, air, air, _public_inputs_ok)
 
 
 # ---- Pedersen proofs that bind their statement: h_i = pedersen_hash(x_i, y_i) for k given triples -----------------
@@ -906,86 +967,13 @@ def verify_hashes(proof, final_log: int = 6, n_queries: int = None) -> Tuple[boo
     points as the sum (sp_felt_add_dev) of sp_air_eval_points_dev for the eleven AIR constraints and
     sp_hash_io_boundary_points_dev for the three boundary quotients, which takes the public polynomials'
     coefficients from three inverse ntt calls made once per proof."""
-    try:
-        if not (isinstance(proof, dict) and proof.get("air") == HASH_IO_AIR):
-            return False, "malformed"
-        view = dict(proof, air="pedersen")  # the shape rules and the Merkle part are the Pedersen AIR's
-        if not (_wellformed(view) and _is_int(final_log) and 0 <= final_log <= 30):
-            return False, "malformed"
-    except Exception:  # an object that misbehaves when inspected is malformed too
-        return False, "malformed"
-    spec = AIRS["pedersen"]
-    n, seed, shift = proof["n"], proof["seed"], proof["shift"]
-    pub = list(proof.get("public_inputs", ()))
-    if len(pub) != 3 * (n // 512) or not all(_is_felt(v) for v in pub):
-        return False, "public inputs"
-    m = n << BLOWUP_LOG
-    log_m = m.bit_length() - 1
-    root_t, roots, final, queries = proof["trace_root"], proof["layer_roots"], proof["final_layer"], proof["queries"]
-    n_layers = log_m - final_log
-    if len(roots) != n_layers or len(final) != 1 << final_log or n_layers < 1:
-        return False, "shape"
-    if n_queries is not None and n_queries != len(queries):
-        return False, "shape"
-    if any(len(q["layers"]) != n_layers for q in queries):
-        return False, "malformed"
-    tr = Transcript(HASH_IO_AIR, n, shift, seed, pub)
-    tr.absorb("trace_root", root_t)
-    alphas = [tr.challenge("alpha", k) for k in range(spec["n_constraints"] + N_HASH_IO_ALPHAS)]
-    betas = []
-    for k in range(n_layers):
-        tr.absorb("layer_root", roots[k])
-        betas.append(tr.challenge("beta", k + 1))
-    tr.absorb("final_layer", *final)
-    indices = [tr.challenge("query", qi, modulus=m // 2) for qi in range(len(queries))]
-    torch = _torch()
-    final_t = felts_to_tensor(final)
-    coeffs = tensor_to_felts(ntt(final_t, inverse=True))
-    if any(c != 0 for c in coeffs[3 * n >> n_layers:]):
-        return False, "final layer degree"
-    if not queries:
-        return True, "ok"
-    openings = iter(check_merkle_openings(view))
-    per = periodic_lde(n, shift, "cuda", "pedersen")
-    dev = per.device
-    positions = torch.tensor([pos for j in indices for pos in (j, j + m // 2)], dtype=torch.int64, device=dev)
-    cur = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side]["values"]], dev)
-    nxt = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side + 1]["values"]], dev)
-    shape = (positions.shape[0], spec["n_cols"], 4)
-    cur, nxt = cur.reshape(shape), nxt.reshape(shape)
-    comp, comp_st = air_eval_points("pedersen", n, per, alphas[:spec["n_constraints"]], shift, positions, cur, nxt)
-    bnd, bnd_st = hash_io_boundary_points(n, hash_io_coefficients(pub, n, dev), alphas[spec["n_constraints"]:], shift,
-                                          positions, cur)
-    comp = felt_add(comp, bnd)
-    pairs = felts_to_tensor([o["value"] for q in queries for pair in q["layers"] for o in pair], dev)
-    fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
-                                pairs.reshape(len(queries), n_layers, 2, 4), final_t)
-    comp, fold_st = tensor_to_felts(comp), fold_st.cpu().tolist()
-    comp_st = [a | b for a, b in zip(comp_st.cpu().tolist(), bnd_st.cpu().tolist())]
-    for qi, (q, j) in enumerate(zip(queries, indices)):
-        trace_ok = [next(openings)[1] for _ in range(4)]
-        layer_ok = [[next(openings)[1] for _ in range(2)] for _ in range(n_layers)]
-        if q["index"] != j:
-            return False, "query index"
-        if [t["row"] for t in q["trace"]] != [j, (j + 4) % m, j + m // 2, (j + m // 2 + 4) % m]:
-            return False, "trace rows"
-        if not all(trace_ok):
-            return False, "trace path"
-        for side in (0, 1):
-            if comp_st[2 * qi + side] != POINT_OK or q["layers"][0][side]["value"] != comp[2 * qi + side]:
-                return False, "composition value"
-        jk, mk = j, m
-        for k in range(n_layers):
-            jk %= mk // 2
-            a, b = q["layers"][k]
-            if (a["pos"], b["pos"]) != (jk, jk + mk // 2):
-                return False, "layer positions"
-            if not all(layer_ok[k]):
-                return False, "layer path"
-            if fold_st[qi][k] != FOLD_OK:
-                return False, "fold consistency at layer %d" % k
-            mk //= 2
-    return True, "ok"
+    def public_ok(air, n, pub):
+        return len(pub) == 3 * (n // 512) and all(_is_felt(v) for v in pub)
+
+    def boundary_at(pub, n, alphas, shift, positions, cur, dev):
+        return hash_io_boundary_points(n, hash_io_coefficients(pub, n, dev), alphas, shift, positions, cur)
+    return _verify_trace_proof(proof, final_log, n_queries, HASH_IO_AIR, "pedersen", public_ok,
+                               (N_HASH_IO_ALPHAS, boundary_at))
 
 
 # ---- boundary constraints from a descriptor: ECDSA and range-check proofs that bind their statement --------------
@@ -1189,90 +1177,14 @@ def prove_ranges(values, n_queries: int = 8, seed: int = 0, final_log: int = 6, 
 
 
 def _verify_bound(name, proof, final_log, n_queries):
-    """verify_hashes for a named descriptor of BOUNDARY_DESCRIPTORS: the same reasons in the same order."""
+    """The verifier core for a named descriptor of BOUNDARY_DESCRIPTORS: the statement rules are the base AIR's."""
     desc = BOUNDARY_DESCRIPTORS[name]
-    air = desc["air"]
-    try:
-        if not (isinstance(proof, dict) and proof.get("air") == name):
-            return False, "malformed"
-        view = dict(proof, air=air)  # the shape rules, the statement rules and the Merkle part are the base AIR's
-        if not (_wellformed(view) and _is_int(final_log) and 0 <= final_log <= 30):
-            return False, "malformed"
-    except Exception:  # an object that misbehaves when inspected is malformed too
-        return False, "malformed"
-    spec = AIRS[air]
-    n, seed, shift = proof["n"], proof["seed"], proof["shift"]
-    pub = list(proof.get("public_inputs", ()))
-    if not _public_inputs_ok(air, n, pub):
-        return False, "public inputs"
-    m = n << BLOWUP_LOG
-    log_m = m.bit_length() - 1
-    root_t, roots, final, queries = proof["trace_root"], proof["layer_roots"], proof["final_layer"], proof["queries"]
-    n_layers = log_m - final_log
-    if len(roots) != n_layers or len(final) != 1 << final_log or n_layers < 1:
-        return False, "shape"
-    if n_queries is not None and n_queries != len(queries):
-        return False, "shape"
-    if any(len(q["layers"]) != n_layers for q in queries):
-        return False, "malformed"
-    tr = Transcript(name, n, shift, seed, pub)
-    tr.absorb("trace_root", root_t)
-    nc = spec["n_constraints"]
-    alphas = [tr.challenge("alpha", k) for k in range(nc + len(desc["terms"]))]
-    betas = []
-    for k in range(n_layers):
-        tr.absorb("layer_root", roots[k])
-        betas.append(tr.challenge("beta", k + 1))
-    tr.absorb("final_layer", *final)
-    indices = [tr.challenge("query", qi, modulus=m // 2) for qi in range(len(queries))]
-    torch = _torch()
-    final_t = felts_to_tensor(final)
-    coeffs = tensor_to_felts(ntt(final_t, inverse=True))
-    if any(c != 0 for c in coeffs[3 * n >> n_layers:]):
-        return False, "final layer degree"
-    if not queries:
-        return True, "ok"
-    openings = iter(check_merkle_openings(view))
-    per = periodic_lde(n, shift, "cuda", air)
-    dev = per.device
-    positions = torch.tensor([pos for j in indices for pos in (j, j + m // 2)], dtype=torch.int64, device=dev)
-    cur = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side]["values"]], dev)
-    nxt = felts_to_tensor([v for q in queries for side in (0, 1) for v in q["trace"][2 * side + 1]["values"]], dev)
-    shape = (positions.shape[0], spec["n_cols"], 4)
-    cur, nxt = cur.reshape(shape), nxt.reshape(shape)
-    comp, comp_st = air_eval_points(air, n, per, alphas[:nc], shift, positions, cur, nxt)
-    coef = boundary_coefficients(desc, boundary_term_values(name, pub), n, alphas[nc:], dev)
-    bnd, bnd_st = boundary_points(desc, n, coef, alphas[nc:], shift, positions, cur)
-    comp = felt_add(comp, bnd)
-    pairs = felts_to_tensor([o["value"] for q in queries for pair in q["layers"] for o in pair], dev)
-    fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
-                                pairs.reshape(len(queries), n_layers, 2, 4), final_t)
-    comp, fold_st = tensor_to_felts(comp), fold_st.cpu().tolist()
-    comp_st = [a | b for a, b in zip(comp_st.cpu().tolist(), bnd_st.cpu().tolist())]
-    for qi, (q, j) in enumerate(zip(queries, indices)):
-        trace_ok = [next(openings)[1] for _ in range(4)]
-        layer_ok = [[next(openings)[1] for _ in range(2)] for _ in range(n_layers)]
-        if q["index"] != j:
-            return False, "query index"
-        if [t["row"] for t in q["trace"]] != [j, (j + 4) % m, j + m // 2, (j + m // 2 + 4) % m]:
-            return False, "trace rows"
-        if not all(trace_ok):
-            return False, "trace path"
-        for side in (0, 1):
-            if comp_st[2 * qi + side] != POINT_OK or q["layers"][0][side]["value"] != comp[2 * qi + side]:
-                return False, "composition value"
-        jk, mk = j, m
-        for k in range(n_layers):
-            jk %= mk // 2
-            a, b = q["layers"][k]
-            if (a["pos"], b["pos"]) != (jk, jk + mk // 2):
-                return False, "layer positions"
-            if not all(layer_ok[k]):
-                return False, "layer path"
-            if fold_st[qi][k] != FOLD_OK:
-                return False, "fold consistency at layer %d" % k
-            mk //= 2
-    return True, "ok"
+
+    def boundary_at(pub, n, alphas, shift, positions, cur, dev):
+        coef = boundary_coefficients(desc, boundary_term_values(name, pub), n, alphas, dev)
+        return boundary_points(desc, n, coef, alphas, shift, positions, cur)
+    return _verify_trace_proof(proof, final_log, n_queries, name, desc["air"], _public_inputs_ok,
+                               (len(desc["terms"]), boundary_at))
 
 
 def verify_signatures(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]:
@@ -1730,14 +1642,11 @@ def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[b
         return False, "public inputs"
     m = n << BLOWUP_LOG
     log_m = m.bit_length() - 1
-    roots, final, queries = proof["layer_roots"], proof["final_layer"], proof["queries"]
+    queries = proof["queries"]
     n_layers = log_m - final_log
-    if len(roots) != n_layers or len(final) != 1 << final_log or n_layers < 1:
-        return False, "shape"
-    if n_queries is not None and n_queries != len(queries):
-        return False, "shape"
-    if any(len(q["layers"]) != n_layers for q in queries):
-        return False, "malformed"
+    reason = _fri_shape_reason(proof, n_layers, final_log, n_queries)
+    if reason:
+        return False, reason
     flat_pub = [len(segments)] + [BUILTIN_SEGMENTS.index(s) for s in segments]
     if has_rc:
         flat_pub += [rc_min, rc_max]
@@ -1750,17 +1659,12 @@ def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[b
         z = tr.challenge("rc16_z")
         tr.absorb("phase2_root", proof["phase2_root"])
     alphas = [tr.challenge("alpha", k) for k in range(n_alphas)]
-    betas = []
-    for k in range(n_layers):
-        tr.absorb("layer_root", roots[k])
-        betas.append(tr.challenge("beta", k + 1))
-    tr.absorb("final_layer", *final)
-    indices = [tr.challenge("query", qi, modulus=m // 2) for qi in range(len(queries))]
+    betas, indices = _replay_fri_challenges(tr, proof, m)
     torch = _torch()
-    final_t = felts_to_tensor(final)
-    coeffs = tensor_to_felts(ntt(final_t, inverse=True))  # the zero pattern of the interpolant's, as in verify
-    if any(c != 0 for c in coeffs[3 * n >> n_layers:]):
-        return False, "final layer degree"
+    final_t = felts_to_tensor(proof["final_layer"])
+    reason = _final_layer_reason(final_t, n, n_layers)
+    if reason:
+        return False, reason
     if not queries:
         return True, "ok"
     openings = iter(check_builtins_openings(dict(proof, phase2_root=proof["phase2_root"] if has_rc else None)))
@@ -1785,12 +1689,9 @@ def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[b
         comp, comp_st = builtins_eval_points(segments, n, pers, alphas, shift, z, rc_min, rc_max,
                                              torch.tensor(positions, dtype=torch.int64, device=dev),
                                              cur.reshape(shape), nxt.reshape(shape), pcur, pnxt)
-    pairs = felts_to_tensor([o["value"] for q in queries for pair in q["layers"] for o in pair], dev)
-    fold_st = fri_check_queries(log_m, betas, shift, torch.tensor(indices, dtype=torch.int64, device=dev),
-                                pairs.reshape(len(queries), n_layers, 2, 4), final_t)
+    fold_st = _fold_statuses(queries, indices, betas, shift, log_m, final_t, dev)
     if shaped:
         comp, comp_st = tensor_to_felts(comp), comp_st.cpu().tolist()
-    fold_st = fold_st.cpu().tolist()
     for qi, (q, j) in enumerate(zip(queries, indices)):
         phase1_ok, phase2_ok = [], []
         for _ in range(4):
@@ -1810,18 +1711,7 @@ def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[b
                 return False, "phase 1 path"
         if not all(phase2_ok):
             return False, "phase 2 path"
-        for side in (0, 1):
-            if comp_st[2 * qi + side] != POINT_OK or q["layers"][0][side]["value"] != comp[2 * qi + side]:
-                return False, "composition value"
-        jk, mk = j, m
-        for k in range(n_layers):
-            jk %= mk // 2
-            a, b = q["layers"][k]
-            if (a["pos"], b["pos"]) != (jk, jk + mk // 2):
-                return False, "layer positions"
-            if not all(layer_ok[k]):
-                return False, "layer path"
-            if fold_st[qi][k] != FOLD_OK:
-                return False, "fold consistency at layer %d" % k
-            mk //= 2
+        reason = _composition_reason(q, qi, comp, comp_st) or _layers_reason(q, j, m, layer_ok, fold_st[qi])
+        if reason:
+            return False, reason
     return True, "ok"

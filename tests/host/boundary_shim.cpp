@@ -69,10 +69,10 @@ int bs_points(unsigned log_period, unsigned n_cols, unsigned n_groups, const uns
       boundary_point_store(false, FE_ZERO, i, out, status);
       continue;
     }
-    const fe x = boundary_point_x(prm, pos[i]);
+    const fe x = boundary_point_x(prm.shift, prm.w, prm.log_n, pos[i]);
     for (unsigned lane = 0; lane < BND_POINT_TPB; ++lane)
       for (unsigned d = 0; d < n_groups; ++d)
-        share[d * BND_POINT_TPB + lane] = boundary_lane_share(prm, log_period, coef, x, d, lane);
+        share[d * BND_POINT_TPB + lane] = boundary_lane_share(prm.log_n, log_period, prm.arg[d], coef, x, d, lane);
     for (unsigned half = BND_POINT_TPB / 2; half > 0; half >>= 1)
       for (unsigned lane = 0; lane < half; ++lane)
         for (unsigned d = 0; d < n_groups; ++d)

@@ -43,7 +43,7 @@ int hs_points(unsigned log_n, const uint64_t* coef, const uint64_t* alphas, cons
               const uint64_t* pos, const uint64_t* cur, uint64_t* out, uint8_t* status, char* err, size_t err_len) {
   if (const char* bad = hash_io_points_check_args(log_n, n)) return refuse(bad, err, err_len);
   if (n == 0) return 0;
-  if (const char* bad = hash_io_points_check_pointers(coef, alphas, shift, pos, cur, out, status))
+  if (const char* bad = boundary_points_check_pointers(coef, alphas, shift, pos, cur, out, status))
     return refuse(bad, err, err_len);
   if (!shift_ok(shift, log_n)) return refuse("bad shift", err, err_len);
   HashIoPointParams prm;
@@ -51,18 +51,19 @@ int hs_points(unsigned log_n, const uint64_t* coef, const uint64_t* alphas, cons
   std::vector<fe> share(3 * HIO_POINT_TPB);
   for (size_t i = 0; i < n; ++i) {  // one block per point
     if (!hash_io_point_ok(log_n, pos, cur, i)) {
-      hash_io_point_store(false, FE_ZERO, i, out, status);
+      boundary_point_store(false, FE_ZERO, i, out, status);
       continue;
     }
-    const fe x = hash_io_point_x(prm, pos[i]);
+    const fe x = boundary_point_x(prm.shift, prm.w, prm.log_n, pos[i]);
     for (unsigned lane = 0; lane < HIO_POINT_TPB; ++lane)
-      for (unsigned c = 0; c < 3; ++c) share[c * HIO_POINT_TPB + lane] = hash_io_lane_share(prm, coef, x, c, lane);
+      for (unsigned c = 0; c < 3; ++c)
+        share[c * HIO_POINT_TPB + lane] = boundary_lane_share(prm.log_n, 9, prm.arg[c], coef, x, c, lane);
     for (unsigned half = HIO_POINT_TPB / 2; half > 0; half >>= 1)
       for (unsigned lane = 0; lane < half; ++lane)
         for (unsigned c = 0; c < 3; ++c)
           share[c * HIO_POINT_TPB + lane] =
-              hash_io_share_add(share[c * HIO_POINT_TPB + lane], share[c * HIO_POINT_TPB + lane + half]);
-    hash_io_point_store(true, hash_io_point_value(prm, x, cur + 16 * i, share[0], share[HIO_POINT_TPB],
+              boundary_share_add(share[c * HIO_POINT_TPB + lane], share[c * HIO_POINT_TPB + lane + half]);
+    boundary_point_store(true, hash_io_point_value(prm, x, cur + 16 * i, share[0], share[HIO_POINT_TPB],
                                                   share[2 * HIO_POINT_TPB]), i, out, status);
   }
   return 0;
