@@ -984,6 +984,55 @@ int sp_boundary_points_dev(unsigned log_period, unsigned n_cols, unsigned n_grou
                            size_t n_points, const uint64_t* pos, const uint64_t* cur, uint64_t* out, uint8_t* status,
                            void* stream);
 
+/* Boundary constraints of the builtins proof (starkperp.stark.prove_builtin_usage /
+ * verify_builtin_usage).  The combined builtin trace lays the present segments (`segments`: SP_SEG_* bits, 1 .. 7)
+ * side by side - 4 + 10 + 3 columns - each with its own period p_s (512, 1024, 8) and k_s = n / p_s instances.  Every
+ * segment brings the groups and terms of a descriptor of the pair above, columns relative to its first column:
+ *     pedersen   {9, 4, 3, {0, 256, 511}, 3, {0, 0, 1}, {0, 1, 2}}                 s = x | s = y | px = h
+ *     ecdsa      {10, 10, 3, {0, 256, 512}, 5, {0, 0, 3, 4, 0}, {0, 1, 1, 1, 2}}   m = z | m = r, qx, qy | m = w
+ *     rc16       {3, 3, 1, {7}, 1, {1}, {0}}                                       acc = value_i at row 8 i + 7
+ * and B(x) is the sum over ALL 3 + 3 + 1 groups of the quotient above, each with its own segment's p and k.  The
+ * 3 + 5 + 1 challenges stand in segment order.  Conventions are those of the pair above: DEVICE arrays of packed
+ * felts, HOST challenges and shift, enqueued on `stream`, nothing waited for, SP_ERR_BAD_ARGUMENT - sp_last_error()
+ * naming the call and the argument - before anything is launched or written, the launches of a call bracketed by
+ * sp_profile_begin / sp_profile_end as one entry (units = points, for the combine call items).
+ *
+ * sp_boundary_combine_dev: the public columns before extension, out[d][i] = sum_{t in d} a_t v_t[i] mod p, canonical,
+ *   for i < k - what every caller of the pair above does "before any extension", here on the device.
+ *     n_groups 1 .. 4, n_terms 1 .. 8, term_groups[t] < n_groups with every group used (host array)
+ *     values_host  HOST array of n_terms DEVICE columns of k felts each (any 256-bit value), in term order
+ *     alphas_host  n_terms felts;  k  1 .. 2^30;  out  n_groups x k felts, no column of values_host
+ *   One launch, one item per lane, at most three products behind a reduction.
+ * sp_builtins_boundary_dev: out[j] = (acc ? acc[j] : 0) + B(x_j) mod p for every j < M = 4 * 2^log_n.
+ *     trace_lde    the committed phase-1 LDE: the 4 + 10 + 3 columns of the present segments, col_stride >= M apart
+ *     pub_lde      3 + 3 + 1 columns of M felts, the present segments' groups in order: C_d at x_j g^-o_d - one
+ *                  sp_lde_dev call per group, k_s points at log_blowup log_period_s + 2 with the shift shift g^-o_d
+ *     alphas_host  3 + 5 + 1 felts of the present segments;  acc  NULL, or M felts; may be `out`
+ *     log_n        the largest minimum of the present segments (9, 10, 3) .. 24;  shift_host: the pair's rule
+ *   ONE table-build launch writes every group's 4 p_s inverse denominators into a per-stream table (at most 3 * 2048 +
+ *   3 * 4096 + 32 felts, nothing that grows with M), ONE elementwise launch follows, one point per lane.  With one
+ *   segment the result is sp_boundary_dev's with that descriptor, bit for bit.
+ * sp_builtins_boundary_points_dev: B at n_points LDE positions, canonically what the dense call adds at index pos[i].
+ *     coef         the groups' coefficient arrays back to back, natural order: 3 k_pedersen, 3 k_ecdsa, k_rc16 felts -
+ *                  sp_ntt_dev(inverse = 1) of the combined public columns
+ *     pos[i]       LDE index below M (u64);  cur: n_points x n_cols felts, the WHOLE opened phase-1 row at pos[i]
+ *     out[i]       the value;  status[i] = SP_POINT_OK, or SP_POINT_OUT_OF_RANGE with out[i] = 0 when pos[i] >= M or
+ *                  any felt of the row is not below p (nothing is read out of bounds for any pos[i])
+ *     log_n        from the same minimum up to 30, 24 with rc16 (sp_builtins_eval_points_dev's bound);  n_points at
+ *                  most 2^30, 0 is SP_OK without a launch
+ *   ONE launch, one block of 256 lanes per point; the segments run one after the other through the same 36 KiB of
+ *   LDS, each as sp_boundary_points_dev runs its descriptor, and lane 0 keeps the running sum.  About
+ *   sum_d k_d / 256 multiplications per lane: with rc16 at n = 2^23 that is 4096 Horner steps. */
+int sp_boundary_combine_dev(unsigned n_groups, unsigned n_terms, const unsigned* term_groups,
+                            const uint64_t* const* values_host, size_t k, const uint64_t* alphas_host, uint64_t* out,
+                            void* stream);
+int sp_builtins_boundary_dev(unsigned segments, unsigned log_n, const uint64_t* trace_lde, size_t col_stride,
+                             const uint64_t* pub_lde, const uint64_t* alphas_host, const uint64_t* shift_host,
+                             const uint64_t* acc, uint64_t* out, void* stream);
+int sp_builtins_boundary_points_dev(unsigned segments, unsigned log_n, const uint64_t* coef, const uint64_t* alphas_host,
+                                    const uint64_t* shift_host, size_t n_points, const uint64_t* pos, const uint64_t* cur,
+                                    uint64_t* out, uint8_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ void release_ec_points_state(); // per-lane ladder tables (ec_points.hip)
 void release_commit_open_state();  // per-stream opening metadata (commit_open.hip)
 void release_hash_io_state();   // per-stream denominator tables (hash_io.hip)
 void release_boundary_state();  // per-stream denominator tables (boundary.hip)
+void release_builtins_boundary_state();  // the same of builtins_boundary.hip
 
 std::recursive_mutex& global_mu() {
   static std::recursive_mutex mu;
@@ -651,6 +652,7 @@ void sp_shutdown(void) {
   sp::release_commit_open_state();
   sp::release_hash_io_state();
   sp::release_boundary_state();
+  sp::release_builtins_boundary_state();
   sp::release_tree_state();
   sp::release_host_lanes();
   for (int i = 0; i < SP_MAX_CONTEXTS; ++i) {

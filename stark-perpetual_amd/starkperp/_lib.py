@@ -136,7 +136,13 @@ _SIGNATURES = {
     "sp_boundary_points_dev": (ctypes.c_int, [ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p, ctypes.c_uint,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 5),
-    "sp_tree_create": (ctypes.c_int, [ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
+    "sp_boundary_combine_dev": (ctypes.c_int, [ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sp_builtins_boundary_dev": (ctypes.c_int, [ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p, ctypes.c_size_t]
+                                 + [ctypes.c_void_p] * 6),
+    "sp_builtins_boundary_points_dev": (ctypes.c_int, [ctypes.c_uint, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 5),
+    "sp_tree_create":(ctypes.c_int, [ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
     "sp_tree_create_on": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
     "sp_order_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint,

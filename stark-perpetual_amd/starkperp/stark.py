@@ -986,6 +986,9 @@ BOUNDARY_DESCRIPTORS = {
     "range_check_io": {"air": "range_check", "rows": (0,), "terms": ((0, 0),)},  # v = value_i at row 0
     # the statement of prove_hashes (which keeps its own kernels): the cross-check of the two implementations
     "pedersen_io": {"air": "pedersen", "rows": HASH_IO_ROWS, "terms": ((0, 0), (0, 1), (1, 2))},
+    # the rc16 segment of a combined builtin trace (prove_builtin_usage): acc = value_i at a value's last limb, row 7.
+    # Period 8 is below what sp_boundary_dev takes: this one runs through sp_builtins_boundary_dev only.
+    "rc16_io": {"air": "rc16", "rows": (7,), "terms": ((1, 0),)},
 }
 
 
@@ -1215,6 +1218,12 @@ def verify_ranges(proof, final_log: int = 6, n_queries: int = None) -> Tuple[boo
 def rc16_fill(values, total_values):
     """values (each < 2^128) -> (padded list of total_values values, rc_min, rc_max); the padding values' limbs
     fill the holes of the limb range (the builtin's unused cells)."""
+    pads, filler, lo, hi = _rc16_fill_parts(values, total_values)
+    return list(values) + pads + [filler] * (total_values - len(values) - len(pads)), lo, hi
+
+
+def _rc16_fill_parts(values, total_values):
+    """(pads, filler, rc_min, rc_max) of rc16_fill: everything but the padded list itself."""
     limbs = set()
     for v in values:
         assert 0 <= v < 1 << 128
@@ -1230,7 +1239,19 @@ def rc16_fill(values, total_values):
     if len(values) + len(pads) > total_values:
         raise ValueError("the trace is too short to fill the %d holes of the limb range" % len(holes))
     filler = sum(lo << (16 * k) for k in range(RC16_LIMBS))
-    return list(values) + pads + [filler] * (total_values - len(values) - len(pads)), lo, hi
+    return pads, filler, lo, hi
+
+
+def rc16_fill_tensor(values, total_values, device="cuda"):
+    """(padded [total_values, 4] device tensor, rc_min, rc_max): rc16_fill without total_values Python integers - the
+    given values and the pads are converted, the filler is broadcast (NumPy)."""
+    import numpy as np
+    pads, filler, lo, hi = _rc16_fill_parts(values, total_values)
+    head = list(values) + pads
+    arr = np.empty((total_values, 4), dtype="<i8")
+    arr[:] = np.frombuffer(filler.to_bytes(32, "little"), dtype="<i8")
+    arr[:len(head)] = np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in head), dtype="<i8").reshape(-1, 4)
+    return _torch().from_numpy(arr).to(device), lo, hi
 
 
 def rc16_columns(values):
@@ -1287,15 +1308,20 @@ def prove_builtins(hash_inputs=None, signatures=None, rc_values=None, n_queries:
     cells (16 values).  The trace length is the power of two the largest segment needs; the other segments repeat
     their instances (unused builtin cells).  Two committed phases: the builtin columns, then - after the
     challenge z - the permutation product of the range-check segment.  Benchmark-grade like prove_trace (no
-    boundary constraint ties the instances to the public inputs except rc_min / rc_max; ~2 bits per query).
+    boundary constraint ties the instances to the public inputs except rc_min / rc_max; ~2 bits per query;
+    prove_builtin_usage is this proof with its hashes, signatures and values bound).
     Verifier: verify_builtins (on the GPU; its oracle is oracle/stark_ref.verify_builtins_proof)."""
     return _query_builtins(_commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift, log_rows),
                            n_queries)
 
 
-def _commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift, log_rows):
+def _commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift, log_rows, statement=None):
     """The commit phase of prove_builtins (both committed phases, the composition, the FRI layers); returns what the
-    query phase needs."""
+    query phase needs.  `statement` (prove_builtin_usage), the hook _commit_trace has: a function of what the prover
+    holds once the trace stands - n, the segments, the trace, the instance tensors it was built from - that returns
+    (name, public, flat_pub, n_extra, add): the AIR name, the public inputs and their flat transcript list taken
+    instead of this function's, how many challenges are drawn after the AIRs' own in the same way, and
+    add(trace_lde, comp, extra_alphas) -> comp of what they bring to the composition."""
     torch = _torch()
     dev = "cuda"
     P = FIELD_PRIME
@@ -1326,19 +1352,30 @@ def _commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift,
             assert 0 < z_ < 2**251 and 1 <= r_ < 2**251 and 1 <= w_ < 2**251
         public["signatures"] = [[z_, r_, s_, q[0], q[1]] for z_, r_, s_, q in sigs]
         flat_pub += [v for sig in public["signatures"] for v in sig]
+    held = {"n": n, "segments": segments}  # what a statement hook may read
     if hash_inputs:
         hs = _cycle(list(hash_inputs), n // 512)
-        groups.append(pedersen_trace(felts_to_tensor([x for x, _ in hs], dev), felts_to_tensor([y for _, y in hs], dev)))
+        held["hashes"] = hs
+        held["hash_xy"] = (felts_to_tensor([x for x, _ in hs], dev), felts_to_tensor([y for _, y in hs], dev))
+        groups.append(pedersen_trace(*held["hash_xy"]))
     if signatures:
-        groups.append(ecdsa_trace(*(felts_to_tensor(v, dev) for v in (
+        held["sig_zrwq"] = tuple(felts_to_tensor(v, dev) for v in (
             [z_ for z_, _, _, _ in sigs], [r_ for _, r_, _, _ in sigs], ws, [q[0] for *_, q in sigs],
-            [q[1] for *_, q in sigs]))))
+            [q[1] for *_, q in sigs]))
+        groups.append(ecdsa_trace(*held["sig_zrwq"]))
     if rc_values:
-        groups.append(rc16_columns(felts_to_tensor(padded, dev)))
+        held["rc_padded"] = felts_to_tensor(padded, dev)
+        groups.append(rc16_columns(held["rc_padded"]))
     trace = torch.cat(groups)
     del groups
     n_cols = trace.shape[0]
-    tr = Transcript("builtins", n, shift, seed, flat_pub)
+    name, n_extra, add = "builtins", 0, None
+    if statement is not None:
+        held["trace"] = trace
+        name, public, flat_pub, n_extra, add = statement(dict(held, public=public))
+        rc_min, rc_max = public.get("rc_min", rc_min), public.get("rc_max", rc_max)  # a lying claim, consistently
+    del held
+    tr = Transcript(name, n, shift, seed, flat_pub)
     # ---- phase 1: the builtin columns ----
     trace_lde = lde(trace)
     lv1 = commit_rows(trace_lde)
@@ -1355,7 +1392,7 @@ def _commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift,
         tr.absorb("phase2_root", root2)
     del trace
     n_alphas = sum(AIRS[s]["n_constraints"] for s in segments)
-    alphas = [tr.challenge("alpha", k) for k in range(n_alphas)]
+    alphas = [tr.challenge("alpha", k) for k in range(n_alphas + n_extra)]
     comp, c0, a0 = None, 0, 0
     for seg in segments:
         spec = AIRS[seg]
@@ -1367,6 +1404,8 @@ def _commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift,
         comp = part if comp is None else felt_add(comp, part)
         c0 += spec["n_cols"]
         a0 += spec["n_constraints"]
+    if add is not None:
+        comp = add(trace_lde, comp, alphas[n_alphas:])
     layers, level_bufs, roots = [comp], [], []
     s = shift
     while True:
@@ -1385,7 +1424,7 @@ def _commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift,
     tr.absorb("final_layer", *final)
     return {"tr": tr, "M": M, "trace_lde": trace_lde, "lv1": lv1, "p_lde": p_lde, "lv2": lv2, "layers": layers,
             "level_bufs": level_bufs,
-            "head": {"n": n, "air": "builtins", "segments": segments, "seed": seed, "shift": shift,
+            "head": {"n": n, "air": name, "segments": segments, "seed": seed, "shift": shift,
                      "public_inputs": public, "phase1_root": root1, "phase2_root": root2, "layer_roots": roots,
                      "final_layer": final}}
 
@@ -1532,12 +1571,13 @@ def check_builtins_openings(proof) -> List[Tuple[str, bool]]:
     return list(zip(labels, [bool(v) for v in ok]))
 
 
-def _wellformed_builtins(proof):
+def _wellformed_builtins(proof, name="builtins"):
     """_wellformed for a prove_builtins proof: the keys and types, every felt in [0, p), every integer an int, every
     path of its tree's height.  What the oracle answers with a reason - the segment list's contents, the public
     inputs' values, the lengths of layer_roots and final_layer, the number of values of a phase-1 row - is left to
-    verify_builtins."""
-    if not isinstance(proof, dict) or proof.get("air", "builtins") != "builtins":
+    verify_builtins.  With name = "builtins_io" (prove_builtin_usage) the proof must carry that name and the public
+    inputs the bound statement adds, every one an integer below 2^256."""
+    if not isinstance(proof, dict) or proof.get("air", "builtins" if name == "builtins" else None) != name:
         return False
     segments, n, shift = proof.get("segments"), proof.get("n"), proof.get("shift")
     if not (isinstance(segments, (list, tuple)) and all(isinstance(s, str) for s in segments)):
@@ -1562,6 +1602,13 @@ def _wellformed_builtins(proof):
         if not (isinstance(sigs, (list, tuple)) and all(
                 isinstance(sig, (list, tuple)) and len(sig) == 5 and all(_is_int(v) and 0 <= v < 1 << 256 for v in sig)
                 for sig in sigs)):
+            return False
+    if name == BUILTINS_IO_AIR:
+        word = lambda v: _is_int(v) and 0 <= v < 1 << 256
+        if has_rc and not (isinstance(pub.get("rc_values"), (list, tuple)) and all(word(v) for v in pub["rc_values"])):
+            return False
+        if "pedersen" in segments and not (isinstance(pub.get("hashes"), (list, tuple)) and all(
+                isinstance(t, (list, tuple)) and len(t) == 3 and all(word(v) for v in t) for t in pub["hashes"])):
             return False
     if not (_felt_list(proof.get("layer_roots")) and _felt_list(proof.get("final_layer"))):
         return False
@@ -1617,8 +1664,20 @@ def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[b
     The caveat of prove_trace holds here too: this verifies a benchmark-grade argument, NOT a sound proof system -
     no boundary constraint binds the instances to the public inputs except rc_min / rc_max (the rest is only
     absorbed, and checked as the oracle does), and Q queries at blowup 4 give about 2 Q bits."""
+    return _verify_builtins_proof(proof, final_log, n_queries)
+
+
+def _verify_builtins_proof(proof, final_log, n_queries, statement=None):
+    """The one verifier of prove_builtins-shaped proofs; verify_builtins and verify_builtin_usage are its wrappers and
+    document it.  `statement`, when given, is (name, public_ok, flat, n_extra, boundary_at) - what _verify_trace_proof
+    takes as `name` and `boundary`: the AIR name the proof and the transcript carry; public_ok(pub, n, segments), the
+    statement's further rules ("public inputs", after the unbound proof's own); flat(pub, segments), the transcript
+    list; n_extra(segments) more alphas drawn after the AIRs' own; and boundary_at(pub, n, segments, extra_alphas,
+    shift, positions, cur, dev) -> (values, status) at the opened points, added to the composition value
+    (sp_felt_add_dev), its status ORed into the points'."""
+    name, public_ok, flat_of, n_extra_of, boundary_at = statement or ("builtins", None, None, None, None)
     try:
-        if not (_wellformed_builtins(proof) and _is_int(final_log) and 0 <= final_log <= 30):
+        if not (_wellformed_builtins(proof, name) and _is_int(final_log) and 0 <= final_log <= 30):
             return False, "malformed"
     except Exception:  # an object that misbehaves when inspected is malformed too
         return False, "malformed"
@@ -1640,6 +1699,8 @@ def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[b
             return False, "public inputs"
     if "pedersen" in segments and n % 512:
         return False, "public inputs"
+    if public_ok is not None and not public_ok(pub, n, segments):
+        return False, "public inputs"
     m = n << BLOWUP_LOG
     log_m = m.bit_length() - 1
     queries = proof["queries"]
@@ -1647,18 +1708,22 @@ def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[b
     reason = _fri_shape_reason(proof, n_layers, final_log, n_queries)
     if reason:
         return False, reason
-    flat_pub = [len(segments)] + [BUILTIN_SEGMENTS.index(s) for s in segments]
-    if has_rc:
-        flat_pub += [rc_min, rc_max]
-    if "ecdsa" in segments:
-        flat_pub += [v for sig in pub["signatures"] for v in sig]
-    tr = Transcript("builtins", n, shift, seed, flat_pub)
+    if flat_of is not None:
+        flat_pub = flat_of(pub, segments)
+    else:
+        flat_pub = [len(segments)] + [BUILTIN_SEGMENTS.index(s) for s in segments]
+        if has_rc:
+            flat_pub += [rc_min, rc_max]
+        if "ecdsa" in segments:
+            flat_pub += [v for sig in pub["signatures"] for v in sig]
+    n_extra = n_extra_of(segments) if n_extra_of else 0
+    tr = Transcript(name, n, shift, seed, flat_pub)
     tr.absorb("phase1_root", proof["phase1_root"])
     z = 0
     if has_rc:
         z = tr.challenge("rc16_z")
         tr.absorb("phase2_root", proof["phase2_root"])
-    alphas = [tr.challenge("alpha", k) for k in range(n_alphas)]
+    alphas = [tr.challenge("alpha", k) for k in range(n_alphas + n_extra)]
     betas, indices = _replay_fri_challenges(tr, proof, m)
     torch = _torch()
     final_t = felts_to_tensor(proof["final_layer"])
@@ -1686,9 +1751,13 @@ def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[b
             pcur = felts_to_tensor([q["phase2"][2 * side]["value"] for q in head for side in (0, 1)], dev)
             pnxt = felts_to_tensor([q["phase2"][2 * side + 1]["value"] for q in head for side in (0, 1)], dev)
         shape = (len(positions), n_cols, 4)
-        comp, comp_st = builtins_eval_points(segments, n, pers, alphas, shift, z, rc_min, rc_max,
-                                             torch.tensor(positions, dtype=torch.int64, device=dev),
-                                             cur.reshape(shape), nxt.reshape(shape), pcur, pnxt)
+        positions = torch.tensor(positions, dtype=torch.int64, device=dev)
+        cur = cur.reshape(shape)
+        comp, comp_st = builtins_eval_points(segments, n, pers, alphas[:n_alphas], shift, z, rc_min, rc_max, positions,
+                                             cur, nxt.reshape(shape), pcur, pnxt)
+        if boundary_at is not None:
+            bnd, bnd_st = boundary_at(pub, n, segments, alphas[n_alphas:], shift, positions, cur, dev)
+            comp, comp_st = felt_add(comp, bnd), comp_st | bnd_st
     fold_st = _fold_statuses(queries, indices, betas, shift, log_m, final_t, dev)
     if shaped:
         comp, comp_st = tensor_to_felts(comp), comp_st.cpu().tolist()
@@ -1715,3 +1784,257 @@ def verify_builtins(proof, final_log: int = 6, n_queries: int = None) -> Tuple[b
         if reason:
             return False, reason
     return True, "ok"
+
+
+# ---- the builtins proof bound to its statement: hashes, signatures, range-checked values --------------------------
+# DESIGN.md 6.6.  Every present segment of the combined trace brings the boundary groups of its descriptor - pedersen_io,
+# ecdsa_io, rc16_io - with challenges of its own (3 + 5 + 1, drawn after the 11 + 26 + 8 of the AIRs); B is the sum over
+# all groups, each with its own segment's period.  Definition in integers: tests/builtins_io_ref.py (on
+# oracle/stark_ref.py and tests/boundary_ref.py); kernels: csrc/builtins_boundary.hip.
+BUILTINS_IO_AIR = "builtins_io"
+BUILTIN_BOUNDARY = {"pedersen": "pedersen_io", "ecdsa": "ecdsa_io", "rc16": "rc16_io"}  # segment -> its descriptor
+
+
+def _builtin_boundary_shape(segments):
+    """(terms, groups) of the present segments' descriptors together."""
+    descs = [BOUNDARY_DESCRIPTORS[BUILTIN_BOUNDARY[s]] for s in segments]
+    return sum(len(d["terms"]) for d in descs), sum(len(d["rows"]) for d in descs)
+
+
+def _ordered_segments(segments):
+    segments = list(segments)
+    assert segments and segments == [s for s in BUILTIN_SEGMENTS if s in segments]
+    return segments
+
+
+def boundary_combine(term_groups, n_groups, columns, alphas):
+    """[n_groups, k, 4]: out[d][i] = sum_{t in d} a_t v_t[i] mod p on the device (sp_boundary_combine_dev) - what
+    _boundary_combined does in Python integers, bit for bit.  `columns`: one [k, 4] device tensor per term (any layout;
+    made contiguous here), term_groups[t] the term's group."""
+    import ctypes
+    torch = _torch()
+    lib = _lib.ensure_init()
+    columns = [c.contiguous() for c in columns]
+    k = columns[0].shape[0]
+    assert len(columns) == len(alphas) == len(term_groups) and all(tuple(c.shape) == (k, 4) for c in columns)
+    out = torch.empty((n_groups, k, 4), dtype=torch.int64, device=columns[0].device)
+    _lib.check(lib.sp_boundary_combine_dev(n_groups, len(columns), (ctypes.c_uint * len(columns))(*term_groups),
+                                           (ctypes.c_void_p * len(columns))(*[c.data_ptr() for c in columns]), k,
+                                           pack_felts(alphas), out.data_ptr(), _stream()), "sp_boundary_combine_dev")
+    return out
+
+
+def _builtin_combined(segments, columns, alphas):
+    """Per present segment the [n_groups, k_s, 4] combined public columns; `columns`: segment -> its terms' tensors."""
+    out, a0 = [], 0
+    for seg in segments:
+        terms = BOUNDARY_DESCRIPTORS[BUILTIN_BOUNDARY[seg]]["terms"]
+        out.append(boundary_combine([d for _, d in terms], 1 + max(d for _, d in terms), columns[seg],
+                                    alphas[a0 : a0 + len(terms)]))
+        a0 += len(terms)
+    return out
+
+
+def builtins_boundary_public_lde(segments, columns, n, alphas, shift=FIELD_GEN):
+    """[3 + 3 + 1, 4n, 4] of the present segments: per group C_d at x_j g^-o_d.  The terms' public columns are combined
+    on the device, then ONE sp_lde_dev call per group writes its column of the result (k_s points at blowup 4 p_s)."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    segments = _ordered_segments(segments)
+    g = _root_of_unity(n)
+    combined = _builtin_combined(segments, columns, alphas)
+    out = torch.empty((_builtin_boundary_shape(segments)[1], 4 * n, 4), dtype=torch.int64, device=combined[0].device)
+    at = 0
+    for seg, comb in zip(segments, combined):
+        period = AIRS[seg]["period"]
+        assert comb.shape[1] == n // period
+        for d, o in enumerate(BOUNDARY_DESCRIPTORS[BUILTIN_BOUNDARY[seg]]["rows"]):
+            _lib.check(lib.sp_lde_dev(comb[d].data_ptr(), out[at].data_ptr(), 1, comb.shape[1].bit_length() - 1,
+                                      period.bit_length() + 1, pack_felts([shift * pow(g, -o, FIELD_PRIME) % FIELD_PRIME]),
+                                      _stream()), "sp_lde_dev")
+            at += 1
+    return out
+
+
+def builtins_boundary(segments, trace_lde, pub_lde, n, alphas, shift=FIELD_GEN, acc=None, out=None):
+    """out[j] = (acc[j] if acc is given else 0) + B(x_j) on the whole LDE coset (sp_builtins_boundary_dev): trace_lde
+    the committed phase-1 LDE of the present segments, pub_lde from builtins_boundary_public_lde with the same
+    alphas.  `out` may be `acc`."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    segments = _ordered_segments(segments)
+    M = 4 * n
+    n_terms, n_groups = _builtin_boundary_shape(segments)
+    assert len(alphas) == n_terms and trace_lde.shape[0] == sum(AIRS[s]["n_cols"] for s in segments)
+    assert trace_lde.shape[1] == M and tuple(pub_lde.shape) == (n_groups, M, 4) and pub_lde.is_contiguous()
+    _, _, stride = _table_shape(trace_lde)
+    if out is None:
+        out = torch.empty((M, 4), dtype=torch.int64, device=trace_lde.device)
+    assert tuple(out.shape) == (M, 4) and out.is_contiguous() and (acc is None or (tuple(acc.shape) == (M, 4)
+                                                                                    and acc.is_contiguous()))
+    _lib.check(lib.sp_builtins_boundary_dev(sum(SEG_BITS[s] for s in segments), n.bit_length() - 1, trace_lde.data_ptr(),
+                                            stride, pub_lde.data_ptr(), pack_felts(alphas), pack_felts([shift]),
+                                            None if acc is None else acc.data_ptr(), out.data_ptr(), _stream()),
+               "sp_builtins_boundary_dev")
+    return out
+
+
+def builtins_boundary_coefficients(segments, columns, n, alphas):
+    """[3 k_pedersen + 3 k_ecdsa + k_rc16, 4]: the coefficients, in natural order, of every group's C_d back to back
+    (combined on the device, one inverse ntt call per group; at k = 1 they are the values)."""
+    torch = _torch()
+    segments = _ordered_segments(segments)
+    parts = []
+    for comb in _builtin_combined(segments, columns, alphas):
+        parts += [col if col.shape[0] == 1 else ntt(col, inverse=True) for col in comb]
+    return torch.cat(parts).contiguous()
+
+
+def builtins_boundary_points(segments, n, coef, alphas, shift, pos, cur):
+    """B at arbitrary LDE positions from opened rows (sp_builtins_boundary_points_dev): coef from
+    builtins_boundary_coefficients with the same alphas, pos [q] int64 tensor of LDE indices, cur [q, n_cols, 4] the
+    WHOLE phase-1 rows there.  Returns (out [q, 4], status [q] uint8)."""
+    torch = _torch()
+    lib = _lib.ensure_init()
+    segments = _ordered_segments(segments)
+    q = pos.shape[0]
+    n_cols = sum(AIRS[s]["n_cols"] for s in segments)
+    n_coef = sum(len(BOUNDARY_DESCRIPTORS[BUILTIN_BOUNDARY[s]]["rows"]) * (n // AIRS[s]["period"]) for s in segments)
+    assert len(alphas) == _builtin_boundary_shape(segments)[0] and tuple(coef.shape) == (n_coef, 4) and coef.is_contiguous()
+    assert pos.dtype == torch.int64 and pos.is_contiguous() and cur.is_contiguous() and tuple(cur.shape) == (q, n_cols, 4)
+    out = torch.empty((q, 4), dtype=torch.int64, device=cur.device)
+    status = torch.empty((q,), dtype=torch.uint8, device=cur.device)
+    _lib.check(lib.sp_builtins_boundary_points_dev(sum(SEG_BITS[s] for s in segments), n.bit_length() - 1,
+                                                   coef.data_ptr(), pack_felts(alphas), pack_felts([shift]), q,
+                                                   pos.data_ptr(), cur.data_ptr(), out.data_ptr(), status.data_ptr(),
+                                                   _stream()), "sp_builtins_boundary_points_dev")
+    return out, status
+
+
+def _builtin_usage_flat(pub, segments):
+    """The flat transcript list of a builtins_io statement: the segment ids, then rc_min, rc_max, the count and the
+    values, then the signatures, then the hash triples."""
+    flat = [len(segments)] + [BUILTIN_SEGMENTS.index(s) for s in segments]
+    if "rc16" in segments:
+        flat += [pub["rc_min"], pub["rc_max"], len(pub["rc_values"])] + list(pub["rc_values"])
+    if "ecdsa" in segments:
+        flat += [v for sig in pub["signatures"] for v in sig]
+    if "pedersen" in segments:
+        flat += [v for triple in pub["hashes"] for v in triple]
+    return flat
+
+
+def _builtin_usage_columns(pub, n, segments, dev, padded=None):
+    """segment -> the public value column of each of its terms, as device tensors, from a statement's public inputs:
+    x, y, h | z, r, Qx, Qy, w = s^-1 mod N (ONE modular inversion) | the padded rc16 values (rc16_fill_tensor)."""
+    cols = {}
+    if "pedersen" in segments:
+        cols["pedersen"] = [felts_to_tensor([t[c] for t in pub["hashes"]], dev) for c in range(3)]
+    if "ecdsa" in segments:
+        sigs = pub["signatures"]
+        cols["ecdsa"] = [felts_to_tensor(v, dev) for v in ([s[0] for s in sigs], [s[1] for s in sigs], [s[3] for s in sigs],
+                                                           [s[4] for s in sigs],
+                                                           _inverses_mod([s[2] for s in sigs], EC_ORDER))]
+    if "rc16" in segments:
+        cols["rc16"] = [padded if padded is not None else rc16_fill_tensor(pub["rc_values"], n // RC16_LIMBS, dev)[0]]
+    return cols
+
+
+def prove_builtin_usage(hash_inputs=None, signatures=None, rc_values=None, n_queries: int = 8, seed: int = 0,
+                        final_log: int = 6, shift: int = FIELD_GEN, log_rows: int = None, claims=None):
+    """prove_builtins as a proof of a STATEMENT: arguments, trace, phases, FRI and query phase are prove_builtins's, and
+    the public inputs (a dict, AIR name "builtins_io", the keys of the present segments only) are bound:
+      hashes      one [x, y, h] per Pedersen instance of the trace (n / 512, the caller's list cycled): h = H(x, y);
+      signatures  one [z, r, s, Qx, Qy] per ECDSA instance (n / 1024, cycled): a signature the reference accepts;
+      rc_values   the caller's values with rc_min, rc_max: each below 2^128.  The rc16 segment holds
+                  rc16_fill(rc_values, n / 8) - the values, the hole-filling pads, the filler - a function of
+                  rc_values and n that the verifier recomputes.
+    On top of the 11 + 26 + 8 constraints the present segments bring the 3 + 5 + 1 boundary terms of pedersen_io,
+    ecdsa_io and rc16_io (acc at row 8 i + 7 is the i-th padded value) with challenges of their own, drawn after the
+    AIRs'.  The public value columns come from tensors the prover holds (h is px at rows 512 i + 511 of the trace),
+    are combined on the device (sp_boundary_combine_dev), extended with one sp_lde_dev call per group and enter the
+    composition through ONE sp_builtins_boundary_dev call.  `claims`, when given, is a dict that replaces any of
+    "hashes", "signatures", "rc_values" of the public inputs - in the transcript, the composition and FRI alike; it
+    exists so that a test can make the prover lie consistently: such a proof is rejected ("final layer degree").
+    Verifier: verify_builtin_usage (verify and verify_builtins answer "malformed").
+
+    What still is not: no zero knowledge, and Q queries at blowup 4 give about 2 Q bits of soundness."""
+    claims = dict(claims or {})
+    assert set(claims) <= {"hashes", "signatures", "rc_values"}
+
+    def statement(held):
+        n, segments, dev = held["n"], held["segments"], held["trace"].device
+        assert set(claims) <= {{"pedersen": "hashes", "ecdsa": "signatures", "rc16": "rc_values"}[s] for s in segments}
+        public, given, padded = {}, {}, None  # `given`: the columns the prover holds already
+        if "rc16" in segments:
+            if "rc_values" in claims:
+                public["rc_values"] = [int(v) for v in claims["rc_values"]]
+                _, _, public["rc_min"], public["rc_max"] = _rc16_fill_parts(public["rc_values"], n // RC16_LIMBS)
+            else:
+                public.update(held["public"], rc_values=[int(v) for v in rc_values])
+                public.pop("signatures", None)
+                padded = held["rc_padded"]
+        if "ecdsa" in segments:
+            public["signatures"] = [[int(v) for v in sig] for sig in claims.get("signatures", held["public"]["signatures"])]
+            assert len(public["signatures"]) == n // 1024
+            if "signatures" not in claims:
+                z_t, r_t, w_t, qx_t, qy_t = held["sig_zrwq"]
+                given["ecdsa"] = [z_t, r_t, qx_t, qy_t, w_t]
+        if "pedersen" in segments:
+            if "hashes" in claims:
+                public["hashes"] = [[int(v) for v in t] for t in claims["hashes"]]
+                assert len(public["hashes"]) == n // 512
+            else:
+                h_t = held["trace"][1, 511::512].contiguous()
+                public["hashes"] = [[x, y, h] for (x, y), h in zip(held["hashes"], tensor_to_felts(h_t))]
+                given["pedersen"] = list(held["hash_xy"]) + [h_t]
+        columns = dict(_builtin_usage_columns(public, n, [s for s in segments if s not in given], dev, padded), **given)
+
+        def add_boundary(trace_lde, comp, alphas):
+            pub_lde = builtins_boundary_public_lde(segments, columns, n, alphas, shift)
+            return builtins_boundary(segments, trace_lde, pub_lde, n, alphas, shift, acc=comp, out=comp)
+        return (BUILTINS_IO_AIR, public, _builtin_usage_flat(public, segments), _builtin_boundary_shape(segments)[0],
+                add_boundary)
+    return _query_builtins(_commit_builtins(hash_inputs, signatures, rc_values, seed, final_log, shift, log_rows,
+                                            statement), n_queries)
+
+
+def verify_builtin_usage(proof, final_log: int = 6, n_queries: int = None) -> Tuple[bool, str]:
+    """Verifier of prove_builtin_usage: (True, "ok") says that every [x, y, h] of public_inputs["hashes"] is a
+    Pedersen hash, every [z, r, s, Qx, Qy] of ["signatures"] a signature the reference accepts and every value of
+    ["rc_values"] below 2^128 - the instances of the trace ARE the published ones - up to the soundness of the
+    argument: about 2 Q bits for Q queries at blowup 4, and no zero knowledge.  Reasons, their order and the
+    "malformed" rules are verify_builtins's; "public inputs", at that reason's turn, also for a list of the wrong
+    length (n / 512 triples, n / 1024 signatures), a hash value that is no felt, a range-checked value of 2^128 or more,
+    values whose fill does not fit the n / 8 cells, and rc_min / rc_max other than the fill's.  A proof of another AIR
+    is "malformed" here, as this AIR is for verify and verify_builtins.
+
+    Where it runs: as verify_builtins, with 3 + 5 + 1 more alphas.  The public inputs are packed on the host - the
+    padded range-check list by rc16_fill_tensor, w_i = s_i^-1 mod N behind one modular inversion - combined on the
+    device (sp_boundary_combine_dev) and turned into coefficients by one inverse ntt per group, once per proof; ONE
+    sp_builtins_boundary_points_dev launch gives B at the 2 Q opened points, added with sp_felt_add_dev."""
+    kept = {}
+
+    def public_ok(pub, n, segments):
+        if "pedersen" in segments and not (len(pub["hashes"]) == n // 512 and all(_is_felt(v) for t in pub["hashes"]
+                                                                                   for v in t)):
+            return False
+        if "rc16" in segments:
+            values = pub["rc_values"]
+            if not values or not all(v < 1 << RANGE_CHECK_BITS for v in values):
+                return False
+            try:
+                kept["padded"], lo, hi = rc16_fill_tensor(values, n // RC16_LIMBS, "cpu")
+            except ValueError:  # the fill does not fit
+                return False
+            if (lo, hi) != (pub["rc_min"], pub["rc_max"]):
+                return False
+        return True
+
+    def boundary_at(pub, n, segments, alphas, shift, positions, cur, dev):
+        padded = kept["padded"].to(dev) if "rc16" in segments else None
+        coef = builtins_boundary_coefficients(segments, _builtin_usage_columns(pub, n, segments, dev, padded), n, alphas)
+        return builtins_boundary_points(segments, n, coef, alphas, shift, positions, cur)
+    return _verify_builtins_proof(proof, final_log, n_queries,
+                                  (BUILTINS_IO_AIR, public_ok, _builtin_usage_flat,
+                                   lambda segments: _builtin_boundary_shape(segments)[0], boundary_at))
